@@ -49,6 +49,8 @@ def parse():
     ap.add_argument("--no-miou", action="store_true")
     ap.add_argument("--profile-steps", type=int, default=2)
     ap.add_argument("--all-kernels", default="", help="write EVERY kernel record of the instrumented pass (the JSON line keeps the top 12) to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -121,6 +123,36 @@ def miou_parity(dgtd, dev, n: int = 256, size: int = 64, bs: int = 32, log=lambd
             "what": f"{n} synthetic {size}x{size} samples, filler weights, fp32 parity mode, predict path (cod.py:152-153, :219)"}
 
 
+DUMP_SAMPLE = 1 << 22      # elements of a fixed, seeded sample taken from an output too large to write whole (16 MB in fp32)
+
+
+def _sample(flat: torch.Tensor, seed: int) -> torch.Tensor:
+    """``flat`` itself when small, else DUMP_SAMPLE of its elements at fixed seeded positions (identical for the same length)."""
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(outdir: str, train: bool, loss: torch.Tensor, prob, net) -> None:
+    """What the last timed step handed its caller, as float32 / float64 .npy files (well under 64 MB in all):
+    train: ``loss`` (the step's return value), ``params_sample`` (a seeded sample of every fp32 master parameter after the step's
+    AdamW update, in named_parameters order) and ``params_sums`` (per parameter: sum and sum of absolute values, float64);
+    predict: ``prob`` (the probability map, sampled when larger than DUMP_SAMPLE elements)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    save = lambda name, t: np.save(os.path.join(outdir, name + ".npy"), t.detach().cpu().numpy())
+    with torch.no_grad():
+        if train:
+            save("loss", loss.detach().double().reshape(1))
+            ps = [p.detach().reshape(-1) for _, p in net.named_parameters()]
+            save("params_sample", _sample(torch.cat([p.float() for p in ps]), seed=0))
+            save("params_sums", torch.stack([torch.stack([p.double().sum(), p.double().abs().sum()]) for p in ps]))
+        else:
+            save("prob", _sample(prob.detach().float().reshape(-1), seed=1))
+
+
 def main():
     args = parse()
     # stdout carries exactly ONE line, the result JSON: keep a private handle to it and point fd 1 at stderr so that library
@@ -175,10 +207,13 @@ def main():
             reducer.refresh_working()
         return loss
 
+    last = {}
+
     def predict_step(i):
         b = batches[i % len(batches)]
         with torch.no_grad():
             prob, _ = net(b["raw"], b["input"], b["label"], b["depth"], mode="predict")
+        last["prob"] = prob
         return prob.mean()
 
     step = train_step if train else predict_step
@@ -252,6 +287,9 @@ def main():
         # random init at the config's lr 5e-4 (meant for pretrained weights) can diverge on the synthetic batches; NaN is not JSON
         print(f"[bench] final loss is not finite ({final_loss})", file=sys.stderr, flush=True)
         final_loss = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train, loss, last.get("prob"), net)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # ---- instrumented pass: per-call HIP-event timing inside libdgtd.so (not part of `value`)
     roofline, kernels, attention, entries = None, [], [], []

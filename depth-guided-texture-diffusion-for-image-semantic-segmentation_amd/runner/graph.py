@@ -15,8 +15,8 @@ call.  What had to be true for capture to be correct (the round-1 attempt crashe
   once after backward, inside the capture);
 * no torch.cat / torch.stack in the captured region (see ``_no_cat``): that, not the autograd engine, was what made the round-1
   replays produce NaNs;
-* world > 1: with RCCL the bucketed all-reduces are captured too, forked onto the reducer's side stream from the autograd hooks
-  (one graph, collectives overlapped with the rest of backward); with a backend that cannot be captured (gloo) the all-reduce stays
+* world > 1: with RCCL the bucketed all-reduces are captured too, in line on the capture stream (one graph, one chain of nodes; see
+  GraphedTrainStep); with a backend that cannot be captured (gloo) the all-reduce stays
   OUTSIDE the graphs (graph A = forward/backward/gather, eager bucketed all-reduce, graph B = AdamW).
 """
 from __future__ import annotations
@@ -49,6 +49,16 @@ class _no_cat:
         return False
 
 
+class _Done:
+    """A completed collective: its work is already ordered on the stream it was issued on."""
+
+    def wait(self) -> None:
+        pass
+
+
+_DONE = _Done()
+
+
 class GraphedTrainStep:
     """``comm`` decides how the gradient all-reduce of an N > 1 job meets the captured step:
 
@@ -65,6 +75,10 @@ class GraphedTrainStep:
     * ``"split"``: graph A (forward / backward / gather) -> eager bucketed all-reduce -> graph B (AdamW); no overlap, works with any
       backend (the gloo tests).
     * ``"auto"``: fused with RCCL, split otherwise.  World 1 without DGTD_FORCE_ALLREDUCE: one graph, no collective.
+
+    In "fused" and "hooks" the collectives are captured where they are issued, on the capture stream itself (``_launch_inline``), not
+    forked onto the side stream: the recorded graph is one chain without parallel branches, which is what replays reliably (a graph
+    with a side-stream branch per bucket has faulted on replay).  Eager steps outside the graph keep the side-stream overlap.
 
     The eager warm-up steps that precede capture (handles, plans, AccumulateGrad nodes on the capture stream) run on the first batch;
     parameters, optimizer state, BatchNorm statistics, the loss scale and the RNG are snapshotted before and restored after them, so a
@@ -143,6 +157,22 @@ class GraphedTrainStep:
         if r.comm_stream is not None:
             torch.cuda.current_stream().wait_stream(r.comm_stream)
 
+    def _launch_inline(self, bucket) -> None:
+        """Stands in for the reducer's ``_launch`` while the step is warmed up and captured in "fused" / "hooks": the bucket's
+        all-reduces run synchronously, which RCCL issues on the CURRENT stream, instead of being forked onto a side stream.  The
+        bucket's ``works`` get already-complete stand-ins, so ``wait_bucket`` still widens the 16-bit payload in stream order."""
+        import torch.distributed as dist
+        r = self.reducer
+        flat, g16, nw = bucket["flat"], bucket["g16"], bucket["n_work"]
+        avg = dist.get_backend(r.group) == "nccl"
+        op = dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM
+        parts = [flat] if g16 is None else ([g16] + ([flat[nw:]] if flat.numel() > nw else []))
+        for t in parts:
+            if not avg:
+                t.div_(r.world)
+            dist.all_reduce(t, op=op, group=r.group)
+        bucket["works"] = [_DONE] * len(parts)
+
     def _one_step(self) -> torch.Tensor:
         """The step in the order the capture records it (also the eager warm-up)."""
         loss = self._fwd_bwd()
@@ -161,7 +191,8 @@ class GraphedTrainStep:
                 self.opt.step()            # bucket i's AdamW waits for bucket i's all-reduce only
             finally:
                 self.opt.pipelined = False
-            torch.cuda.current_stream().wait_stream(r.comm_stream)     # rejoin the side stream (capture: no unjoined branch)
+            if r.comm_stream is not None:
+                torch.cuda.current_stream().wait_stream(r.comm_stream)     # rejoin the side stream (capture: no unjoined branch)
             r._works.clear()
         else:
             self._gather_all()
@@ -210,6 +241,10 @@ class GraphedTrainStep:
         # hooks: the autograd hooks gather + fork the collectives (eager overlap mode, recorded); fused: they only mark buckets ready and
         # the flush points gather / launch (reducer.set_staged); otherwise they only count and gather / launch are explicit in _one_step
         r.overlap = overlap if self.mode in ("hooks", "fused") else False
+        inline = self.mode in ("hooks", "fused")
+        comm_stream = r.comm_stream
+        if inline:                       # the collectives stay on the capture stream: no parallel branch in the graph
+            r._launch, r.comm_stream = self._launch_inline, None
         try:
             s = self.stream
             s.wait_stream(torch.cuda.current_stream())
@@ -254,6 +289,9 @@ class GraphedTrainStep:
             raise
         finally:
             r.overlap = overlap          # eager steps after (or instead of) the capture keep the reducer's own mode
+            if inline:
+                del r._launch
+                r.comm_stream = comm_stream
         self._pin_arenas(True)
 
     def _pin_arenas(self, on: bool) -> None:

@@ -203,6 +203,40 @@ def gen_model(S: int, B: int, with_grads: bool) -> dict:
     return out
 
 
+def gen_ref32(S: int = 32, B: int = 2) -> dict:
+    """The reference in train mode at 32x32 (filler weights loaded through the state_dict), the case tests/test_oracle_vs_reference.py
+    holds the oracle to: state_dict keys and shapes, loss, every parameter gradient (fp32 as the reference runs; norm, strided samples,
+    +-1 projection), then eval-mode Hitnet outputs with the running statistics that train step left."""
+    from . import cod_cpu
+    ref = ref_loader.build_reference_model(S, train=True)
+    mine = cod_cpu.cod(S).train()
+    filler.fill_module(mine)
+    ref.load_state_dict(mine.state_dict())
+    sd = ref.state_dict()
+    out = {"keys": np.array(list(sd)), "shapes": np.array(["x".join(map(str, v.shape)) for v in sd.values()])}
+    x, d, l = filler.synthetic_batch(B, S)
+    loss = ref(None, x, l, list(d), mode="loss")["loss"]
+    out["train.loss"] = np.float64(loss.item())
+    loss.backward()
+    names, norms, samples, projs = [], [], [], []
+    for k, p in ref.named_parameters():
+        names.append(k)
+        norms.append(-1.0 if p.grad is None else p.grad.double().norm().item())
+        samples.append(np.zeros(GRAD_SAMPLES, np.float32) if p.grad is None else grad_samples(p.grad))
+        projs.append(0.0 if p.grad is None else grad_projection(p.grad))
+    out["train.grad_names"] = np.array(names)
+    out["train.grad_norms"] = np.array(norms, dtype=np.float64)
+    out["train.grad_samples"] = np.stack(samples)
+    out["train.grad_proj"] = np.array(projs, dtype=np.float64)
+    ref.eval()
+    with torch.no_grad():
+        x_hp, P1, P2 = ref.hitnet(x, d)
+    out["eval.x_hp"] = x_hp.numpy()
+    out["eval.P1"] = torch.stack(P1).numpy()
+    out["eval.P2"] = P2.numpy()
+    return out
+
+
 FP64_KEYS = ("prompt_encoder.propagation_weight_regressor.reg.", "prompt_encoder.encoder1.", "prompt_encoder.message_passing.conv.",
              "prompt_encoder.encoder2.downsample_layers.0.", "patch_embed1.proj.")
 
@@ -277,7 +311,9 @@ def main(argv):
     os.makedirs(GOLDEN_DIR, exist_ok=True)
     if not argv or "preprocess" in argv:
         np.savez_compressed(os.path.join(GOLDEN_DIR, "preprocess.npz"), **gen_preprocess())
-    want = set(argv) or {"modules", "model64", "model256", "msda", "grads64_fp64"}
+    want = set(argv) or {"modules", "model64", "model256", "msda", "grads64_fp64", "ref32"}
+    if "ref32" in want:
+        np.savez_compressed(os.path.join(GOLDEN_DIR, "ref32.npz"), **gen_ref32())
     if "grads64_fp64" in want:
         np.savez_compressed(os.path.join(GOLDEN_DIR, "grads64_fp64.npz"), **gen_grads_fp64())
     if "msda" in want:

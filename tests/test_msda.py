@@ -104,9 +104,6 @@ def test_half_inputs_compute_in_float32():
 
 
 # ------------------------------------------------------------------------------------------------ the module-level native binding
-REF_FUNC = "/root/reference/twig/ops/functions/ms_deform_attn_func.py"
-
-
 def test_module_binding_exports_the_reference_callables():
     """twig/ops/src/vision.cpp:13-16: a module named MultiScaleDeformableAttention with ms_deform_attn_forward / _backward."""
     import inspect
@@ -117,23 +114,6 @@ def test_module_binding_exports_the_reference_callables():
     with pytest.raises(Exception, match="HIP device|CPU|cpu"):     # no fallback: a CPU tensor is refused loudly
         v = torch.zeros(1, 4, 1, 4)
         MSDA.ms_deform_attn_forward(v, torch.tensor([[2, 2]]), torch.tensor([0]), torch.zeros(1, 1, 1, 1, 1, 2), torch.ones(1, 1, 1, 1, 1), 1)
-
-
-@pytest.mark.skipif(not os.path.exists(REF_FUNC), reason="the reference tree exists in the build container only")
-def test_reference_function_file_binds_to_the_module_unchanged():
-    """Build container: the reference's own ms_deform_attn_func.py, executed as it is, imports `MultiScaleDeformableAttention` and finds
-    this repository's module - its MSDeformAttnFunction then calls MSDA.ms_deform_attn_forward / _backward of libdgtd.so."""
-    import MultiScaleDeformableAttention as MSDA
-    ns = {"__name__": "ref_ms_deform_attn_func"}
-    exec(compile(open(REF_FUNC).read(), REF_FUNC, "exec"), ns)
-    assert ns["MSDA"] is MSDA
-    fn = ns["MSDeformAttnFunction"]
-    assert issubclass(fn, torch.autograd.Function)
-    # the file's own pure-PyTorch core (ms_deform_attn_func.py:49-71) is what generated tests/golden/msda.npz: one case through it here
-    name = next(iter(mc.CASES))
-    (value, shp, loc, attn, _), y, *_ = _run_oracle(name)
-    got = ns["ms_deform_attn_core_pytorch"](value.detach(), shp, loc.detach(), attn.detach())
-    assert torch.allclose(got, y, rtol=1e-10, atol=1e-14)
 
 
 @pytest.mark.gpu
