@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void conv3x3_fwd_kernel(const T* __restrict__ 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = acc[mt][nt][4 * q + e] + (bz ? (float)bz[co + e] : 0.f);
-          if (act == 1) v = fmaxf(v, 0.f);
+          if (act == 1) v = v < 0.f ? 0.f : v;                                                  // ReLU that keeps NaN (fmaxf maps it to 0)
           else if (act == 2) { v = (float)(bf16_t)v; v = v > 0.f ? v : slope * v; }           // PReLU of the ROUNDED pre-activation (what y2 holds)
           else if (act == 3) {
             const float r = (float)rv[e];

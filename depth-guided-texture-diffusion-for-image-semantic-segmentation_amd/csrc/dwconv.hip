@@ -30,7 +30,7 @@ static bool use_tiled() {
 
 namespace {
 
-__device__ __forceinline__ float gelu_f(float x) { return gelu_fast(x); }        // common.h: erfc by A&S 7.1.26, |err| <= 1.5e-7
+__device__ __forceinline__ float gelu_f(float x) { return gelu_fast(x); }        // common.h: erfc by A&S 7.1.26, |Phi error| <= 5e-7
 __device__ __forceinline__ float gelu_grad_f(float x) { return gelu_grad_fast(x); }
 
 // MODE 0: y = conv(x) + bias          MODE 1: y = gelu(conv(x) + bias)

@@ -14,7 +14,7 @@ namespace {
 
 constexpr int TY = 4, TXW = 16, TXS = 8;   // TXS = strip of outputs a lane computes at a time
 
-__device__ __forceinline__ float gelu_t(float x) { return gelu_fast(x); }        // common.h: erfc by A&S 7.1.26, |err| <= 1.5e-7
+__device__ __forceinline__ float gelu_t(float x) { return gelu_fast(x); }        // common.h: erfc by A&S 7.1.26, |Phi error| <= 5e-7
 __device__ __forceinline__ float gelu_grad_t(float x) { return gelu_grad_fast(x); }
 
 template <typename T> struct Pair2;

@@ -18,7 +18,9 @@
 // (row >> 1) & 7 ON THE GLOBAL SOURCE ADDRESS, which makes every ds_read_b128 fragment read conflict-free (128-byte rows: two rows per
 // 256-byte bank row).  MFMA orientation D^T = B·A^T so a lane owns ONE output row and 4-column runs; the fp32 accumulators go through
 // LDS once and every global access of the epilogue (outputs, residual, saved pre-activation) is a coalesced 16-byte row-major access,
-// all epilogue arithmetic in fp32 with ONE rounding per output.  blockIdx -> tile mapping is XCD-aware (the column tiles of one row
+// all epilogue arithmetic in fp32 with ONE rounding per output, except where a stored intermediate is rounded first on purpose: the GELU
+// epilogue applies the GELU to the ROUNDED pre-activation and the residual epilogue adds s*gamma*y from the ROUNDED y (what the backward
+// reads back), so those outputs are rounded twice.  blockIdx -> tile mapping is XCD-aware (the column tiles of one row
 // panel of A run on one XCD's L2).  MFMA-bound above K ~ 512, HBM-bound below: 2·M·N·K flop over (M·K + N·K + n_out·M·N + ...)·e bytes.
 #include "common.h"
 #include <stdlib.h>
