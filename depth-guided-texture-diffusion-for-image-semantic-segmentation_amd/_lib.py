@@ -104,6 +104,9 @@ SIGNATURES = {
     "dgtd_batchnorm_scratch": (_i64, [_i]),
     "dgtd_batchnorm_fwd": (_i, [_vp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _i64, _i, _f, _f, _i, _i, _vp]),
     "dgtd_batchnorm_bwd": (_i, [_vp, _vp, _fp, _fp, _vp, _fp, _fp, _fp, _i64, _i, _i, _vp]),
+    "dgtd_sod_metrics_workspace": (_i64, [_i]),
+    "dgtd_sod_metrics": (_i, [_vp, _i, _fp, _fp, _vp, _i, _i, _i, _vp]),
+    "dgtd_sod_metrics_accumulate": (_i, [_fp, _i, _fp, _fp, _vp]),
 }
 
 _lib = None

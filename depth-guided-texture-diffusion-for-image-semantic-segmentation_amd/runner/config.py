@@ -87,7 +87,7 @@ class Runner:
     the configs' ``AmpOptimWrapper``.  On CPU (gloo tests of the host logic) it is torch.optim.AdamW over the same groups."""
 
     def __init__(self, cfg: dict, device="cuda", compute_dtype=torch.bfloat16, work_dir="work_dir", log: Callable = print,
-                 rank: int = 0, world: int = 1, seed: int = 0):
+                 rank: int = 0, world: int = 1, seed: int = 0, sod_metrics: Optional[str] = None):
         from ..dist import GradReducer, broadcast_parameters
         self.cfg, self.device, self.work_dir, self.log = cfg, device, work_dir, log
         self.rank, self.world, self.seed = rank, world, seed
@@ -121,7 +121,9 @@ class Runner:
         hooks = cfg.get("default_hooks") or {}
         self.log_interval = int((hooks.get("logger") or {}).get("interval", 50))
         self.ckpt_interval = int((hooks.get("checkpoint") or {}).get("interval", 1))
-        self.evaluators = build_evaluators(cfg.get("val_evaluator"), log)
+        # S/E/F-measure on the device (runner/sod_metrics.py) are opt-in: keyword, else val_cfg.sod_metrics, else "skip"
+        self.sod_metrics = sod_metrics or (cfg.get("val_cfg") or {}).get("sod_metrics") or "skip"
+        self.evaluators = build_evaluators(cfg.get("val_evaluator"), log, sod_metrics=self.sod_metrics)
         self.epoch = 0
 
     # ------------------------------------------------------------------ data
@@ -175,6 +177,8 @@ class Runner:
         for ev in self.evaluators:
             ev.results.clear()
             ev.__dict__.pop("_all", None)
+            if callable(getattr(ev, "reset", None)):
+                ev.reset()
         for batch in loader:
             out = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="predict")
             for ev in self.evaluators:

@@ -10,8 +10,14 @@
 * ``MAE``      = twig/metric/MAE.py:18-33: both maps quantised to uint8, then py_sod_metrics.MAE (third-party, pinned at 1.3.1 in
   requirements.txt:110, absent from the reference tree): gt > 128, pred / 255 min-max normalised per image, mean |pred - gt|.
   Restated from the package's published algorithm; PARITY UNPINNED (no reference fixture exists for it).
-* E/F/S-measure (config/sod.yml:85-88) are pure py_sod_metrics arithmetic and are not restated: the runner logs that they are
-  skipped."""
+* E/F/S-measure (config/sod.yml:85-88, config/cod.yml:124-126) are py_sod_metrics arithmetic.  By default (``sod_metrics="skip"``)
+  the runner logs that they are skipped.  With ``sod_metrics="device"`` (``val_cfg: {sod_metrics: device}`` in the YAML) they are
+  built by runner/sod_metrics.py on the HIP kernels of csrc/sod_metrics.hip: the E-measure restates the reference's own commented
+  copy of the package code (twig/metric/Emeasure.py:51-243), S- and F-measure the package's published algorithm.  PARITY UNPINNED
+  against a real py_sod_metrics run, like ``MAE`` (the package is not available to run here).  One known numeric difference: the
+  package squares a Python float with ``**`` (the C library's ``pow``, not always correctly rounded), the kernels multiply, so an
+  E-measure curve can differ from the package's in the last bit for a small share of foreground counts.
+* WeightedFmeasure (commented out in both configs) stays skipped: it needs an exact Euclidean distance transform."""
 from __future__ import annotations
 
 from typing import Dict, List
@@ -107,17 +113,26 @@ EVALUATORS = {"MAE": MAE, "meanIntersectionOverUnion": MeanIoU, "BinaryMIoU": Bi
 THIRD_PARTY = ("Emeasure", "Fmeasure", "Smeasure", "WeightedFmeasure")   # pure py_sod_metrics arithmetic: skipped with a message
 
 
-def build_evaluators(cfg_list, log=print):
+def build_evaluators(cfg_list, log=print, sod_metrics: str = "skip"):
     """``val_evaluator`` entries by ``type``: this module's restated metrics first, then anything ``@export``-ed under that name
-    (runner/registry.py: the reference's twig/metric classes register themselves there when they can be imported)."""
+    (runner/registry.py: the reference's twig/metric classes register themselves there when they can be imported), then - with
+    ``sod_metrics="device"`` - the device S/E/F-measure of runner/sod_metrics.py, which all share one accumulator (one kernel chain
+    per batch).  ``sod_metrics="skip"`` (the default) logs those three as skipped."""
     from . import registry
+    from .sod_metrics import DEVICE_EVALUATORS, SodAccumulator
+    if sod_metrics not in ("skip", "device"):
+        raise ValueError(f"sod_metrics must be 'skip' or 'device', got {sod_metrics!r}")
     out = []
+    acc = None
     for item in cfg_list or []:
         t = item.get("type") if isinstance(item, dict) else str(item)
         if t in EVALUATORS:
             out.append(EVALUATORS[t]())
         elif t in registry.REGISTRY:
             out.append(registry.build(item if isinstance(item, dict) else {"type": t}))
+        elif sod_metrics == "device" and t in DEVICE_EVALUATORS:
+            acc = acc or SodAccumulator()
+            out.append(DEVICE_EVALUATORS[t](acc))
         elif t in THIRD_PARTY:
             log(f"val_evaluator {t}: third-party py_sod_metrics arithmetic, not restated here - skipped")
         else:

@@ -1,0 +1,118 @@
+"""Device ``Smeasure`` / ``Emeasure`` / ``Fmeasure`` evaluators (twig/metric/{S,E,F}measure.py around py_sod_metrics 1.3.1), opt-in
+with ``build_evaluators(..., sod_metrics="device")`` or ``val_cfg: {sod_metrics: device}``.
+
+Wrapper semantics kept: ``process()`` steps every image of the batch, then appends ONE running value - the package's
+``get_results()`` over every image seen so far: ``sm`` for S, ``em.curve.max()`` for E, ``fm.curve.max()`` for F - and
+``compute_metrics()`` returns the mean of those per-batch values.  The arithmetic is csrc/sod_metrics.hip (see runner/metrics.py
+for what is pinned).  Difference from the reference: state is reset at every ``Runner.validate()`` (``reset()``), where a persistent
+mmengine metric object keeps stepping its py_sod_metrics evaluator across validation passes (with ``val_interval == max_epochs``
+in both configs the reference validates once, so the figures agree there).
+
+The evaluators built for one Runner share one ``SodAccumulator``: the kernel chain runs once per batch however many of the three
+are configured, ``process()`` never synchronises, and the running values go to a growable device buffer that ``compute_metrics()``
+reads once."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional
+
+import torch
+
+from .. import _lib as L
+from ..ops.sod_metrics import STATE, sod_metrics_accumulate, sod_metrics_rows
+
+
+class SodAccumulator:
+    """Device state of the running get_results() of the three evaluators: ``state`` (DGTD_SODM_STATE fp64) and one row
+    (sm, max em, max fm) per batch in ``running``."""
+
+    def __init__(self):
+        self.state: Optional[torch.Tensor] = None
+        self.running: Optional[torch.Tensor] = None
+        self.calls = 0
+        self._last = None
+        self._host = None
+
+    def reset(self) -> None:
+        if self.state is not None:
+            self.state.zero_()
+        self.calls = 0
+        self._last = None
+        self._host = None
+
+    def step(self, k: int, pred: torch.Tensor, gt: torch.Tensor) -> int:
+        """Call ``k`` of one evaluator: the first evaluator to reach a batch runs the kernel chain for it; the others find the same
+        (pred, gt) and reuse its slot."""
+        if k == self.calls - 1 and self._last is not None and self._last[0] is pred and self._last[1] is gt:
+            return k
+        if k != self.calls:
+            raise L.DgtdError("evaluators that share one SodAccumulator must process the same batches in the same order")
+        if self.state is None or self.state.device != pred.device:
+            self.state = torch.zeros(STATE, dtype=torch.float64, device=pred.device)
+            self.running = torch.empty(16, 3, dtype=torch.float64, device=pred.device)
+        if k == self.running.shape[0]:
+            grown = torch.empty(2 * k, 3, dtype=torch.float64, device=pred.device)
+            grown[:k].copy_(self.running)
+            self.running = grown
+        rows = sod_metrics_rows(pred, gt)
+        sod_metrics_accumulate(rows, self.state, self.running[k])
+        self.calls += 1
+        self._last = (pred, gt)
+        self._host = None
+        return k
+
+    def running_values(self) -> List[List[float]]:
+        """[(sm, max em, max fm)] per batch, read from the device once per set of batches."""
+        if self._host is None:
+            self._host = self.running[:self.calls].cpu().tolist() if self.calls else []
+        return self._host
+
+    def summary(self) -> Dict[str, float]:
+        """The final table of the reference's evaluation script (twig/metric/Fmeasure.py:62-74, commented out) over every image seen
+        since the last reset: Smeasure, MAE, adpEm, meanEm, maxEm, adpFm, meanFm, maxFm."""
+        if not self.calls:
+            return {}
+        s = self.state.cpu()
+        n = float(s[0])
+        em, fm = s[8:264] / n, s[264:520] / n
+        return {"Smeasure": float(s[1]) / n, "MAE": float(s[2]) / n, "adpEm": float(s[3]) / n, "meanEm": float(em.mean()),
+                "maxEm": float(em.max()), "adpFm": float(s[4]) / n, "meanFm": float(fm.mean()), "maxFm": float(fm.max())}
+
+
+class _DeviceSodMetric:
+    name = "metric"
+    column = 0
+
+    def __init__(self, accumulator: Optional[SodAccumulator] = None, **_ignored):
+        self.acc = accumulator if accumulator is not None else SodAccumulator()
+        self.results: List[int] = []          # slot index of each process() call (Runner.validate clears the list)
+
+    def reset(self) -> None:
+        self.results.clear()
+        self.acc.reset()
+
+    def process(self, data_batch, data_samples) -> None:
+        pred, gt = data_samples
+        self.results.append(self.acc.step(len(self.results), pred, gt))
+
+    def compute_metrics(self) -> Dict[str, float]:
+        vals = self.acc.running_values()
+        per_batch = [vals[i][self.column] for i in self.results]
+        return {self.name: sum(per_batch) / max(1, len(per_batch))}
+
+    def summary(self) -> Dict[str, float]:
+        return self.acc.summary()
+
+
+class Smeasure(_DeviceSodMetric):
+    name, column = "Smeasure", 0
+
+
+class Emeasure(_DeviceSodMetric):
+    name, column = "Emeasure", 1
+
+
+class Fmeasure(_DeviceSodMetric):
+    name, column = "Fmeasure", 2
+
+
+DEVICE_EVALUATORS = {"Smeasure": Smeasure, "Emeasure": Emeasure, "Fmeasure": Fmeasure}

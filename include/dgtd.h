@@ -412,6 +412,22 @@ int64_t dgtd_preprocess_workspace(int Hin, int Win, int C, int S);
 int dgtd_preprocess(const void* img_u8, void* out, const float* mean_host, const float* std_host, void* workspace, int Hin,
                     int Win, int C, int S, int flip, dgtd_dtype out_dt, dgtd_stream s);
 
+/* ---- Salient-object metrics of the validation loop: S-, E-, F-measure and MAE of py_sod_metrics 1.3.1 ---------------------
+ * (as twig/metric/{S,E,F}measure.py and MAE.py call it; config/sod.yml:85-89, config/cod.yml:123-128).  pred [B,H,W] in pred_dt
+ * (F32 / BF16 / F16, upcast exactly to fp32), gt [B,H,W] fp32, both quantised to uint8 as the wrappers do ((x * 255) truncated).
+ * out [B][DGTD_SODM_ROW] fp64 per image = { mae, sm, adp_em, adp_fm, em_curve[256], fm_curve[256], precision[256], recall[256] };
+ * curve index i <-> threshold 255 - i (py_sod_metrics' order).  workspace: dgtd_sod_metrics_workspace(B) bytes, zeroed on `s`
+ * by the call itself (hipMemsetAsync).  No allocation, no synchronisation, no host read: legal inside stream capture.         */
+#define DGTD_SODM_ROW 1028
+int64_t dgtd_sod_metrics_workspace(int B);
+int dgtd_sod_metrics(const void* pred, dgtd_dtype pred_dt, const float* gt, double* out, void* workspace, int B, int H, int W,
+                     dgtd_stream s);
+/* Running state of the wrappers' get_results() over every image seen: state [DGTD_SODM_STATE] fp64 (zeroed by the caller to
+ * start) = { n, sum sm, sum mae, sum adp_em, sum adp_fm, 0, 0, 0, sum em_curve[256], sum fm_curve[256] }, images added in order.
+ * running_slot [3] fp64 receives (sum sm / n, max(sum em_curve / n), max(sum fm_curve / n)) after this batch of B rows of `out`. */
+#define DGTD_SODM_STATE 520
+int dgtd_sod_metrics_accumulate(const double* out, int B, double* state, double* running_slot, dgtd_stream s);
+
 #ifdef __cplusplus
 }
 #endif
