@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """bench.py — training-step throughput of the HIP-backed `cod` model on synthetic 512x512 RGB-D batches.
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]        (N>1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = forward + loss + backward + gradient all-reduce (RCCL, N>1) + AdamW update, batch 8 per GPU
 (BASELINE.json configs[1]: config/sod.yml model, 512x512, batch 8, bf16).  Rank 0 prints ONE JSON line.
-Inputs are resident in HBM before the timed region.  After the timed region a separate instrumented pass times
-every C-ABI call with HIP events on its launch stream inside libdgtd.so (roofline; attention MFMA utilisation), and
-rank 0 at N=1 reports the mIoU parity pair (HIP vs CPU oracle) and times the CPU oracle on a bounded sample (cpu_baseline).
+Inputs are resident in HBM before the timed region.  A plain run does only what the headline needs: set up, warm up,
+time the K steps, write --dump-outputs, print the line (roofline / entries / kernels / attention_mfma are empty).
+--full adds the measurements that take runs of their own, after the timed region: an instrumented pass that times
+every C-ABI call with HIP events on its launch stream inside libdgtd.so (roofline; attention MFMA utilisation), and at
+N=1 the mIoU parity pair (HIP vs CPU oracle) and the CPU oracle timed on a bounded sample (cpu_baseline).
 Other BASELINE configs: --backbone pvt_v2_b3 (config 3's per-GPU workload), --mode predict --size 1024 --batch 4 --dtype f32
 (config 4), --dtype f16 --batch 16 (config 5's per-GPU workload: fp16 + fp32 masters + dynamic loss scale).
 """
@@ -31,7 +33,7 @@ PEAK = {"hbm": (8000.0, "GB/s"), "mfma_bf16": (2500.0, "TFLOP/s"), "mfma_f16": (
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -45,13 +47,19 @@ def parse():
     ap.add_argument("--backbone", default="pvt_v2_b2", help="pvt_v2_b3 = the tier-B backbone of BASELINE config 3")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="train mode: replay the step as a captured hipGraph (auto: try, fall back to the eager step if capture fails)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-miou", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=2)
-    ap.add_argument("--all-kernels", default="", help="write EVERY kernel record of the instrumented pass (the JSON line keeps the top 12) to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the instrumented per-call pass (roofline, entries, kernels, attention_mfma) and, "
+                         "at N=1, the mIoU parity pair and the CPU oracle baseline; a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-miou", action="store_true", help="--full without the mIoU parity pair")
+    ap.add_argument("--profile-steps", type=int, default=2, help="steps of the instrumented pass (--full; 0 skips it)")
+    ap.add_argument("--all-kernels", default="", help="write EVERY kernel record of the instrumented pass (the JSON line keeps the top 12) to this file (--full)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.all_kernels and not args.full:
+        ap.error("--all-kernels records the instrumented pass, which only --full runs")
+    return args
 
 
 def cpu_baseline(size: int, batch: int, mode: str, log=lambda m: None):
@@ -293,7 +301,8 @@ def main():
 
     # ---- instrumented pass: per-call HIP-event timing inside libdgtd.so (not part of `value`)
     roofline, kernels, attention, entries = None, [], [], []
-    if args.profile_steps > 0:
+    profile = args.full and args.profile_steps > 0
+    if profile:
         # EVERY rank runs the instrumented steps (they are eager training steps: with N > 1 each issues the bucketed all-reduces, which
         # must meet their peers - rank 0 alone would hang against the others' barrier); rank 0 summarises.
         # The timing lives in the C ABI (dgtd_profile_enable), so this pass runs EXACTLY the autograd nodes of the timed step (the
@@ -323,7 +332,7 @@ def main():
         summ = dgtd._lib.profile_native_summary()
         dgtd._lib.profile_native(False)
         log("instrumented pass done")
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and profile:
         mfma_peak = {torch.bfloat16: "mfma_bf16", torch.float16: "mfma_f16", torch.float32: "mfma_f32"}[dtype]
         empty = summ.pop("dgtd_profile_empty", None)
         floor_ms = (empty["ms"] / empty["calls"]) if empty and empty["calls"] else 0.0      # per-call floor of the event bracket itself
@@ -420,10 +429,10 @@ def main():
                        "loss_scale": scaler.get_scale() if scaler is not None else None},
             "roofline": roofline, "entries": entries[:10], "kernels": kernels[:12], "attention_mfma": attention,
         }
-        if world == 1 and not args.no_miou:
+        if args.full and world == 1 and not args.no_miou:
             log("mIoU parity (HIP vs CPU oracle, 256 synthetic samples) ...")
             out["miou"] = miou_parity(dgtd, dev, log=log)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU oracle on a bounded sample ...")
             del net, reducer, opt
             torch.cuda.empty_cache()

@@ -268,7 +268,8 @@ def test_real_model_two_ranks_one_gpu():
 def test_bench_control_flow_two_ranks_one_gpu(tmp_path):
     """`bench.py --gpus N` had never run with N > 1 - rank 0 alone entered the instrumented pass (eager steps
     with bucketed all-reduces) while the others went to the barrier.  Two gloo ranks on the one GPU run the whole script at a small
-    size: graph capture (split mode: gloo cannot be captured), timed steps, the instrumented pass on EVERY rank, one JSON line."""
+    size with --full: graph capture (split mode: gloo cannot be captured), timed steps, the instrumented pass on EVERY rank, one JSON
+    line."""
     import json
     import subprocess
     import sys
@@ -278,7 +279,7 @@ def test_bench_control_flow_two_ranks_one_gpu(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--size", "64", "--batch", "2", "--profile-steps", "1"]
+           "--size", "64", "--batch", "2", "--full", "--profile-steps", "1"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=1100)
     assert p.returncode == 0, p.stdout[-2000:] + "\n" + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/final; rm -rf $O; mkdir -p $O
-python3 bench.py --all-kernels $O/kernels_all.json > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --all-kernels $O/kernels_all.json > $O/bench.json 2> $O/bench.err
 echo "bench: $(python3 -c "import json;d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]);print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'])")"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --no-miou --no-cpu-baseline --profile-steps 0 > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 T=$(ls $O/prof/*kernel_trace.csv | head -1)
