@@ -17,7 +17,11 @@
   against a real py_sod_metrics run, like ``MAE`` (the package is not available to run here).  One known numeric difference: the
   package squares a Python float with ``**`` (the C library's ``pow``, not always correctly rounded), the kernels multiply, so an
   E-measure curve can differ from the package's in the last bit for a small share of foreground counts.
-* WeightedFmeasure (commented out in both configs) stays skipped: it needs an exact Euclidean distance transform."""
+* WeightedFmeasure (commented out in both configs) is skipped by default like the other three.  With ``sod_metrics="device"`` it
+  is built on csrc/wfm.hip: an exact integer nearest-foreground transform, then the package's weighting chain in fp64.  Pinned
+  by tests/golden/wfm.npz, recorded from scipy: ``distance_transform_edt`` with its choice among equidistant pixels (distances
+  and indices bit for bit), ``scipy.ndimage.convolve`` with the 7x7 Gaussian, and the package's formula as restated in
+  tests/_wfm_ref.py.  PARITY UNPINNED against a real py_sod_metrics run, like the other three."""
 from __future__ import annotations
 
 from typing import Dict, List
@@ -117,7 +121,8 @@ def build_evaluators(cfg_list, log=print, sod_metrics: str = "skip"):
     """``val_evaluator`` entries by ``type``: this module's restated metrics first, then anything ``@export``-ed under that name
     (runner/registry.py: the reference's twig/metric classes register themselves there when they can be imported), then - with
     ``sod_metrics="device"`` - the device S/E/F-measure of runner/sod_metrics.py, which all share one accumulator (one kernel chain
-    per batch).  ``sod_metrics="skip"`` (the default) logs those three as skipped."""
+    per batch), and the device WeightedFmeasure, which runs a chain of its own.  ``sod_metrics="skip"`` (the default) logs those
+    four as skipped."""
     from . import registry
     from .sod_metrics import DEVICE_EVALUATORS, SodAccumulator
     if sod_metrics not in ("skip", "device"):

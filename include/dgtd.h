@@ -428,6 +428,28 @@ int dgtd_sod_metrics(const void* pred, dgtd_dtype pred_dt, const float* gt, doub
 #define DGTD_SODM_STATE 520
 int dgtd_sod_metrics_accumulate(const double* out, int B, double* state, double* running_slot, dgtd_stream s);
 
+/* ---- Weighted F-measure (py_sod_metrics 1.3.1 WeightedFmeasure, beta^2 = 1; twig/metric/WeightedFmeasure.py) ------------------
+ * Exact nearest-foreground transform of B masks: gt_mask [B,H,W] uint8 (non-zero = foreground); dist2_out [B,H,W] int32 = squared
+ * Euclidean distance to the nearest foreground pixel, index_out [B,H,W] int32 = its flat index y * W + x within the image.  Equal to
+ * scipy.ndimage.distance_transform_edt(mask == 0, return_indices=True), its choice among equidistant pixels included: per column
+ * the nearest foreground row (the smaller row on a tie), then per row the column j minimising (x - j)^2 + (y - row[j])^2 (the
+ * smallest j on a tie); sqrt(dist2) is scipy's distance.  An image without foreground gets -1 in both outputs.  Integer
+ * arithmetic only.  index_out doubles as the scratch of the column pass.  H and W are at most DGTD_EDT_MAX_W (int32 squared
+ * distances, and one row of candidates in LDS); anything larger is refused with an error status.                                 */
+#define DGTD_EDT_MAX_W 16384
+int dgtd_edt_nearest(const uint8_t* gt_mask, int32_t* dist2_out, int32_t* index_out, int B, int H, int W, dgtd_stream s);
+/* out [B] fp64 = the package's per-image Q.  pred [B,H,W] in pred_dt (F32 / BF16 / F16), gt [B,H,W] fp32, quantised as by
+ * dgtd_sod_metrics; an image whose gt has no foreground pixel scores exactly 0.  workspace: dgtd_wfm_workspace(B, H, W) bytes.
+ * Same size limits as dgtd_edt_nearest.  fp64 sums run in a fixed order (no floating-point atomics): two calls on the same input
+ * are bit-identical.  No allocation, no synchronisation, no host read: legal inside stream capture.                            */
+int64_t dgtd_wfm_workspace(int B, int H, int W);
+int dgtd_wfm(const void* pred, dgtd_dtype pred_dt, const float* gt, double* out, void* workspace, int B, int H, int W,
+             dgtd_stream s);
+/* Running get_results()["wfm"]: state [DGTD_WFM_STATE] fp64 (zeroed by the caller to start) = { n, sum wfm }, images added in
+ * order; running_slot [1] fp64 receives sum wfm / n after this batch of B values of `out`.                                      */
+#define DGTD_WFM_STATE 2
+int dgtd_wfm_accumulate(const double* out, int B, double* state, double* running_slot, dgtd_stream s);
+
 #ifdef __cplusplus
 }
 #endif
