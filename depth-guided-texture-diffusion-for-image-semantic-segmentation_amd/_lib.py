@@ -30,6 +30,9 @@ SIGNATURES = {
     "dgtd_gemm_gelu_bwd_workspace": (_i64, [_i, _i]),
     "dgtd_gemm_gelu_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int), _i, _i, _i, _i, _vp]),
     "dgtd_transpose_batched": (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _i, _vp]),
+    "dgtd_gemm_wgrad_supported": (_i, [_i, _i, _i, _i]),
+    "dgtd_gemm_wgrad_workspace": (_i64, [_i, _i, _i, _i]),
+    "dgtd_gemm_wgrad_batched": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i, _vp]),
     "dgtd_layernorm_fwd": (_i, [_vp, _fp, _fp, _vp, _fp, _fp, _i64, _i, _f, _i, _vp]),
     "dgtd_layernorm_bwd_workspace": (_i64, [_i]),
     "dgtd_layernorm_bwd": (_i, [_vp, _vp, _fp, _fp, _fp, _vp, _fp, _fp, _vp, _i64, _i, _i, _vp]),

@@ -9,8 +9,8 @@
 //   * ⊙ gelu'(pre) + bias-gradient column partials  (input gradient of pwconv2 → gradient of the pre-activation)   grad of :1097-1099
 // The input-gradient GEMMs  dX[M,K] = dY[M,N] · W[N,K]  run through the same kernel on a TRANSPOSED copy of the weight (W^T [K,N] is
 // K-contiguous in the reduction dim N): weights change once per step, the copies are refreshed by ONE batched launch per step
-// (dgtd_transpose_batched), so one kernel shape serves forward and backward.  Weight gradients (dY^T X, reduction over tokens) stay
-// with the batched library GEMM of the deferred phase (csrc_torch/bindings.cpp).
+// (dgtd_transpose_batched), so one kernel shape serves forward and backward.  Weight gradients (dY^T X, reduction over tokens) have a
+// kernel of their own in gemm_wgrad.hip (opt-in, DGTD_OWN_WGRAD=1); by default they stay with the batched library GEMM of the deferred phase.
 //
 // Kernel: 128 x BN x 64 tiles (BN = 128 or 64), 4 waves, wave tile 64x64 / 32x64 of v_mfma_f32_32x32x16_{bf16,f16}; operands staged
 // global -> LDS with 16-byte LDS-DMA (global_load_lds_dwordx4, no VGPR round trip), two LDS stages, the next tile in flight across

@@ -211,6 +211,8 @@ inline void park_gemm(const Hint& h, int which, const Tensor& x2, const Tensor& 
   g_pending_gemm.push_back(PendingGemm{h.group, which, h.idx, x2, dy2, dw.data_ptr(), dy2.size(0), dy2.size(1), x2.size(1)});
 }
 Tensor gemm_dw(const Tensor& dy2, const Tensor& x2);
+static bool own_wgrad_try(at::ScalarType dt, const void* dy, const void* x, void* dw, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t s_dy,
+                          int64_t s_x, int64_t s_dw, const at::TensorOptions& o);
 namespace dgemm_fwd { bool batched_dw(at::ScalarType dt, const void* dy, const void* x, void* dw, int64_t N, int64_t K, int64_t M, int batch, int64_t s_dy,
                                       int64_t s_x, int64_t s_dw, const at::TensorOptions& o); }
 static void flush_gemms(std::vector<PendingGemm>& gs) {
@@ -238,8 +240,9 @@ static void flush_gemms(std::vector<PendingGemm>& gs) {
     int64_t S = n >= 16 ? 1 : std::min<int64_t>(max_split, a.M / 1024);
     while (S > 1 && a.M % S) --S;
     const bool dense = n == 1 || (sx == a.M * a.K && sdy == a.M * a.N && sdw == a.N * a.K);
-    bool done = false;
-    if (S >= 2 && dense) {
+    // own kernel first when switched on (it splits the tokens itself, in fp32); everything below is the library path
+    bool done = own_wgrad_try(a.x.scalar_type(), a.dy.data_ptr(), a.x.data_ptr(), a.dw, a.M, a.N, a.K, n, sdy, sx, sdw, a.x.options());
+    if (!done && S >= 2 && dense) {
       Tensor part = at::empty({n * S, a.N * a.K}, a.x.options());
       if (dgemm_fwd::batched_dw(a.x.scalar_type(), a.dy.data_ptr(), a.x.data_ptr(), part.data_ptr(), a.N, a.K, a.M / S, (int)(n * S), (a.M / S) * a.N,
                                 (a.M / S) * a.K, a.N * a.K, a.x.options())) {
@@ -257,6 +260,22 @@ static void flush_gemms(std::vector<PendingGemm>& gs) {
     }
     i = j;
   }
+}
+
+// tools (tools/bench_wgrad_own.py): the deferred phase's weight-gradient GEMMs of ONE run of n layers on a dense arena triple,
+// dy [n,M,N], x [n,M,K] -> dw [n,N,K], through flush_gemms itself (library or own kernel, as the switch says)
+Tensor wgrad_batched(const Tensor& dy, const Tensor& x) {
+  TORCH_CHECK(dy.dim() == 3 && x.dim() == 3 && dy.size(0) == x.size(0) && dy.size(1) == x.size(1) && dy.scalar_type() == x.scalar_type() &&
+              is16(x.scalar_type()), "wgrad_batched: dy [n,M,N] and x [n,M,K] of one 16-bit dtype");
+  on_device(dy);
+  on_device(x);
+  const int64_t n = x.size(0), M = x.size(1), N = dy.size(2), K = x.size(2);
+  Tensor dw = at::empty({n, N, K}, x.options());
+  std::vector<PendingGemm> gs;
+  for (int64_t i = 0; i < n; ++i)
+    gs.push_back(PendingGemm{0, 0, (int)i, x.select(0, i), dy.select(0, i), (char*)dw.data_ptr() + i * N * K * dw.element_size(), M, N, K});
+  flush_gemms(gs);
+  return dw;
 }
 
 // Deferred WEIGHT GRADIENTS of the single dense 3x3 convolutions (Hitnet CAB bodies, conv4: small maps, 20-40 us launches that
@@ -987,12 +1006,45 @@ inline Tensor gemm_dx(const Tensor& dy2, const Tensor& wc) {                    
     at::mm_out(dx2, dy2, wc);
   return dx2;
 }
+// ------------------------------------------------------------------------------------------------ own weight-gradient GEMM (csrc/gemm_wgrad.hip)
+// Process-wide switch, OFF by default: DGTD_OWN_WGRAD=1 in the environment sets it when the library is loaded, set_own_wgrad() flips it
+// later (tests, tools/bench_wgrad_own.py).  When on, flush_gemms and gemm_dw try dgtd_gemm_wgrad_batched first and keep the library path
+// for what dgtd_gemm_wgrad_supported refuses (a token count that is no multiple of 64, fp32, unaligned or overlapping slots).  The
+// two counters tell a test which way the calls went.
+static std::atomic<bool> g_own_wgrad{[] { const char* e = std::getenv("DGTD_OWN_WGRAD"); return e && std::atoi(e) != 0; }()};
+static std::atomic<int64_t> g_own_wgrad_calls{0}, g_own_wgrad_fallbacks{0};
+inline bool own_wgrad_on() { return g_own_wgrad.load(std::memory_order_relaxed); }
+void set_own_wgrad(bool on) { g_own_wgrad.store(on); }
+bool own_wgrad() { return own_wgrad_on(); }
+int64_t own_wgrad_calls() { return g_own_wgrad_calls.load(); }            // cumulative launches of dgtd_gemm_wgrad_batched
+int64_t own_wgrad_fallbacks() { return g_own_wgrad_fallbacks.load(); }    // cumulative calls that the switch offered and the kernel's gate refused
+static bool own_wgrad_try(at::ScalarType dt, const void* dy, const void* x, void* dw, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t s_dy,
+                          int64_t s_x, int64_t s_dw, const at::TensorOptions& o) {
+  if (!own_wgrad_on()) return false;
+  const int64_t lim = 1ll << 31;
+  const bool ok = is16(dt) && M > 0 && M < lim && N < lim && K < lim && batch >= 1 && batch <= 65535 &&
+                  dgtd_gemm_wgrad_supported((int)M, (int)N, (int)K, dt == at::kHalf ? DGTD_F16 : DGTD_BF16) &&
+                  (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw) & 15) == 0 &&
+                  (batch == 1 || (s_dy >= M * N && s_x >= M * K && s_dw >= N * K && ((s_dy | s_x | s_dw) & 7) == 0));
+  if (!ok) { ++g_own_wgrad_fallbacks; return false; }
+  const int64_t bytes = dgtd_gemm_wgrad_workspace((int)batch, (int)M, (int)N, (int)K);
+  Tensor ws;                                               // fp32 partials [batch][S][N K]; S == 1: the kernel stores dW itself
+  if (bytes > batch * N * K * 4) ws = at::empty({bytes / 4}, o.dtype(at::kFloat));
+  check(dgtd_gemm_wgrad_batched(dy, x, dw, ws.defined() ? ws.data_ptr() : nullptr, (int)batch, (int)M, (int)N, (int)K, s_dy, s_x, s_dw,
+                                dt == at::kHalf ? DGTD_F16 : DGTD_BF16, stream()), "dgtd_gemm_wgrad_batched");
+  ++g_own_wgrad_calls;
+  return true;
+}
 // dW = dY^T X; long token dimensions are split into S batches (library batched GEMM) and summed in fp32: the plain GEMM has only a
 // few hundred output tiles, each reducing over all tokens (latency-bound, tools/bench_gemm.py)
 Tensor gemm_dw(const Tensor& dy2, const Tensor& x2) {                              // [M,N]^T x [M,K] -> [N,K]
   const int64_t M = dy2.size(0), N = dy2.size(1), K = x2.size(1);
   const bool bf = is16(dy2.scalar_type()) && x2.is_contiguous() && M > 0;
   hipStream_t st = (hipStream_t)stream();
+  if (own_wgrad_on() && bf && dy2.is_contiguous()) {
+    Tensor dw = at::empty({N, K}, dy2.options());
+    if (own_wgrad_try(dy2.scalar_type(), dy2.data_ptr(), x2.data_ptr(), dw.data_ptr(), M, N, K, 1, 0, 0, 0, dy2.options())) return dw;
+  }
   static const int64_t max_split = [] { const char* e = std::getenv("DGTD_WGRAD_SPLIT"); return e ? (int64_t)std::atol(e) : (int64_t)32; }();
   const int64_t S = std::min<int64_t>(max_split, M / 1024);
   if (S >= 4 && M % S == 0 && is16(dy2.scalar_type())) {
@@ -1877,6 +1929,11 @@ TORCH_LIBRARY(dgtd, m) {
   m.def("flush_deferred_async() -> ()", &flush_deferred_async);
   m.def("pending_reductions() -> int", &pending_reductions);
   m.def("flushed_reductions() -> int", &flushed_reductions);
+  m.def("wgrad_batched(Tensor dy, Tensor x) -> Tensor", &wgrad_batched);
+  m.def("set_own_wgrad(bool on) -> ()", &set_own_wgrad);
+  m.def("own_wgrad() -> bool", &own_wgrad);
+  m.def("own_wgrad_calls() -> int", &own_wgrad_calls);
+  m.def("own_wgrad_fallbacks() -> int", &own_wgrad_fallbacks);
   m.def("set_shared_deferral(bool on) -> ()", &set_shared_deferral);
   m.def("arena_hint(int group, int idx, int count) -> ()", &arena_hint);
   m.def("arena_roles(int out, int grad_a, int grad_b) -> ()", &arena_roles);

@@ -33,6 +33,19 @@ def ops():
 # ------------------------------------------------------------------------------------------------ runs of identical blocks
 _NEXT_GROUP = [0]
 BATCH_WGRAD = os.environ.get("DGTD_BATCH_WGRAD", "1") != "0"
+# the Linear weight gradients on the package's own kernel (csrc/gemm_wgrad.hip) instead of the library GEMM: off by default.  The binding
+# reads the same variable when it is loaded; set_own_wgrad() flips both later.
+OWN_WGRAD = os.environ.get("DGTD_OWN_WGRAD", "0") not in ("", "0")
+
+
+def set_own_wgrad(on: bool) -> None:
+    """Route the Linear weight gradients of the C++ nodes to dgtd_gemm_wgrad_batched (True) or to the library GEMM (False)."""
+    global OWN_WGRAD
+    nat = ops()
+    if nat is None:
+        raise RuntimeError("the C++ bindings (libdgtd_torch.so) are not loaded: the own weight-gradient kernel is routed there")
+    nat.set_own_wgrad(bool(on))
+    OWN_WGRAD = bool(on)
 
 
 class _Released:

@@ -201,6 +201,20 @@ int dgtd_gemm_gelu_bwd(const void* dy, const void* w_t, const void* pre, void* d
 int dgtd_transpose_batched(const void* const* src, void* const* dst, const int* rows, const int* cols, int n, dgtd_dtype dt,
                            dgtd_stream s);
 
+/* ---- Weight gradients of the Linear layers: the GEMM that reduces over tokens (bf16 / fp16; csrc/gemm_wgrad.hip) ------------------
+ * dw[z][N,K] = sum_m dy[z][m,N] * x[z][m,K] for z < batch; entry z of dy / x / dw starts s_dy / s_x / s_dw ELEMENTS after entry z - 1
+ * (ignored when batch == 1; otherwise at least the dense extent and a multiple of 8).  Both operands are read as they lie (token-major),
+ * fp32 accumulation over ALL tokens, one rounding per output: the token dimension is cut into S chunks of at most 4096 tokens, each
+ * workgroup writes a plain fp32 partial tile into `workspace` ([batch][S][N*K] floats, nothing to zero) and a second launch sums the
+ * chunks in a fixed order (bit-reproducible).  dgtd_gemm_wgrad_workspace returns batch * S * N * K * 4 for the S the host logic picks
+ * (0 for an unsupported shape); when S == 1 (the value equals batch * N * K * 4) the kernel stores dw itself and `workspace` is not
+ * touched and may be NULL.  Shapes: M % 64 == 0, N % 64 == 0, K % 64 == 0, every per-entry extent below 2^31 elements
+ * (dgtd_gemm_wgrad_supported); everything 16-byte aligned.                                                                        */
+int dgtd_gemm_wgrad_supported(int M, int N, int K, dgtd_dtype dt);
+int64_t dgtd_gemm_wgrad_workspace(int batch, int M, int N, int K);
+int dgtd_gemm_wgrad_batched(const void* dy, const void* x, void* dw, void* workspace, int batch, int M, int N, int K, int64_t s_dy,
+                            int64_t s_x, int64_t s_dw, dgtd_dtype dt, dgtd_stream s);
+
 /* ---- Fused structure loss of the five deep-supervision heads (fp32) -------------------------------
  * loss = sum_k mix[k] * cal_loss(bilinear_x(S/hs)(lo[k]), label): twig/model/cod.py:76-85 (weighted BCE + weighted IoU with
  * weit = 1 + 5|avgpool31(gt) - gt|), :137-142 (mix = 0, .2, .4, .6 for P1[0..3], 1 for P2) and the x8 align_corners=False
