@@ -20,15 +20,28 @@ __device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, 
   return p - (a.lr * a.inv_bc1) * (m / denom);
 }
 
-template <typename WT>
+enum { CLIP_OFF = 0, CLIP_COEF = 1, CLIP_VALUE = 2 };
+
+// the un-scaled gradient after clipping: CLIP_COEF multiplies by the global-norm coefficient, CLIP_VALUE clamps to +-c with comparisons
+// that let a NaN through (torch's clamp_); CLIP_OFF is the expression the kernel had before clipping existed
+template <int CLIP>
+__device__ __forceinline__ float clipped(float g, float gs, float c) {
+  if (CLIP == CLIP_COEF) return (g * gs) * c;
+  if (CLIP == CLIP_VALUE) { const float u = g * gs; return u < -c ? -c : (u > c ? c : u); }
+  return g * gs;
+}
+
+template <typename WT, int CLIP>
 __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, WT* __restrict__ w, int64_t n, int64_t head,
                                                          AdamArgs a, const float* __restrict__ amp, const float* __restrict__ lr_dev,
-                                                         const WT* __restrict__ g16) {
+                                                         const WT* __restrict__ g16, const float* __restrict__ clip_coef, float clip_value) {
   // g16 != NULL: the gradient is the 16-bit all-reduce payload itself (same phase as w), g is not read
   // amp = the loss scaler's device state { scale, growth_tracker, 1/scale, found_inf, steps taken } or NULL
   // lr_dev = the learning rate in device memory (a captured hipGraph replays with whatever the schedule wrote there) or NULL
+  // CLIP_COEF: clip_coef = the device scalar dgtd_grad_clip_finalize wrote; CLIP_VALUE: clip_value = the bound
   float gs = 1.f;
+  const float cc = CLIP == CLIP_COEF ? *clip_coef : clip_value;
   if (lr_dev) a.lr = *lr_dev;
   if (amp) {
     if (amp[3] != 0.f) return;                              // overflowed step: parameters, moments and working copies stay as they are
@@ -52,7 +65,7 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
       gv = *reinterpret_cast<const f32x4*>(g + o);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { float mj = mv[j], vj = vv[j]; pv[j] = adam_one(pv[j], gv[j] * gs, mj, vj, a); mv[j] = mj; vv[j] = vj; }
+    for (int j = 0; j < 4; ++j) { float mj = mv[j], vj = vv[j]; pv[j] = adam_one(pv[j], clipped<CLIP>(gv[j], gs, cc), mj, vj, a); mv[j] = mj; vv[j] = vj; }
     *reinterpret_cast<f32x4*>(p + o) = pv;
     *reinterpret_cast<f32x4*>(m + o) = mv;
     *reinterpret_cast<f32x4*>(v + o) = vv;
@@ -69,7 +82,7 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
   if (tid < nscal) {
     const int64_t o = tid < head ? tid : tail0 + (tid - head);
     float mj = m[o], vj = v[o];
-    const float pj = adam_one(p[o], (g16 ? (float)g16[o] : g[o]) * gs, mj, vj, a);
+    const float pj = adam_one(p[o], clipped<CLIP>(g16 ? (float)g16[o] : g[o], gs, cc), mj, vj, a);
     p[o] = pj; m[o] = mj; v[o] = vj;
     if (w) w[o] = (WT)pj;
   }
@@ -91,6 +104,89 @@ __global__ __launch_bounds__(256) void found_inf_kernel(const float* __restrict_
   if (__any(bad) && (threadIdx.x & 63) == 0) *found = 1.f;   // same value from every writer: no atomic needed
 }
 
+// ---- global gradient norm (clip_grad of the reference's optim_wrapper): per-workgroup fp64 partials, then one finalize --------------
+enum { NORM_L2 = 0, NORM_INF = 1 };
+
+// L2: a + x^2, every element widened to fp64 first (fp32 squares overflow from |g| ~ 1.8e19; max_f32^2 fits fp64, so the sum is
+// non-finite iff an element is).  inf: max(a, |x|) that keeps a NaN from either side.
+template <int KIND>
+__device__ __forceinline__ double norm_acc(double a, double x) {
+  if (KIND == NORM_L2) return a + x * x;
+  const double ax = fabs(x);
+  return (ax > a || ax != ax) ? ax : a;
+}
+template <int KIND>
+__device__ __forceinline__ double norm_merge(double a, double b) {
+  if (KIND == NORM_L2) return a + b;
+  return (b > a || b != b) ? b : a;
+}
+
+// fixed order: the 64 lanes of a wave by halving strides, then the waves of the workgroup in index order through LDS; thread 0 returns
+template <int KIND, int WAVES>
+__device__ __forceinline__ double norm_block_reduce(double acc) {
+  __shared__ double red[WAVES];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc = norm_merge<KIND>(acc, __shfl_down(acc, off));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  double r = red[0];
+  if (threadIdx.x == 0) for (int i = 1; i < WAVES; ++i) r = norm_merge<KIND>(r, red[i]);
+  return r;
+}
+
+// partial[blockIdx.x] = sum of squares / max magnitude of this workgroup's grid-stride share of g[0, n).  16-byte loads on the aligned
+// body (four in flight per lane, each with its own accumulator), scalars on the unaligned head / tail.  No atomics: the result is
+// a function of (n, head, grid) alone.
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const T* __restrict__ g, int64_t n, int64_t head, double* __restrict__ partial) {
+  typedef typename Vec16<T>::type V;
+  constexpr int N = Vec16<T>::N;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+  const int64_t body = (n - head) / N;                       // 16-byte groups after the unaligned head
+  const V* __restrict__ gb = reinterpret_cast<const V*>(g + head);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  int64_t i = tid;
+  for (; i + 3 * nth < body; i += 4 * nth) {
+    const V v0 = gb[i], v1 = gb[i + nth], v2 = gb[i + 2 * nth], v3 = gb[i + 3 * nth];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      a0 = norm_acc<KIND>(a0, (double)(float)v0[j]);
+      a1 = norm_acc<KIND>(a1, (double)(float)v1[j]);
+      a2 = norm_acc<KIND>(a2, (double)(float)v2[j]);
+      a3 = norm_acc<KIND>(a3, (double)(float)v3[j]);
+    }
+  }
+  for (; i < body; i += nth) {
+    const V v0 = gb[i];
+#pragma unroll
+    for (int j = 0; j < N; ++j) a0 = norm_acc<KIND>(a0, (double)(float)v0[j]);
+  }
+  // head [0, head) and tail [head + N*body, n): at most 2 (N - 1) scalars
+  const int64_t tail0 = head + body * N, nscal = head + (n - tail0);
+  if (tid < nscal) a1 = norm_acc<KIND>(a1, (double)(float)g[tid < head ? tid : tail0 + (tid - head)]);
+  const double r = norm_block_reduce<KIND, 4>(norm_merge<KIND>(norm_merge<KIND>(a0, a1), norm_merge<KIND>(a2, a3)));
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// One workgroup: every partial of every bucket in index order -> total norm (x 1/scale) rounded ONCE to fp32 -> clip coefficient.
+template <int KIND>
+__global__ __launch_bounds__(1024) void grad_clip_finalize_kernel(const double* __restrict__ partials, int64_t count, float max_norm,
+                                                                  float* __restrict__ amp, float* __restrict__ clip_state) {
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < count; i += 1024) acc = norm_merge<KIND>(acc, partials[i]);
+  const double s = norm_block_reduce<KIND, 16>(acc);
+  if (threadIdx.x != 0) return;
+  double t = KIND == NORM_L2 ? sqrt(s) : s;
+  if (amp) {
+    t *= (double)amp[2];
+    if (!(s - s == 0.0)) amp[3] = 1.f;                       // an inf / NaN gradient: this write is the step's found_inf
+  }
+  const float total = (float)t;
+  const float coef = max_norm / (total + 1e-6f);             // torch.nn.utils.clip_grad_norm_; a NaN stays a NaN through the clamp
+  clip_state[0] = total;
+  clip_state[1] = coef > 1.f ? 1.f : coef;
+}
+
 // GradScaler.update() (torch/amp/grad_scaler.py _amp_update_scale_): state = { scale, growth_tracker, inv_scale, found_inf, steps }.
 __global__ void loss_scale_update_kernel(float* __restrict__ state, float growth, float backoff, int interval) {
   float scale = state[0], tracker = state[1];
@@ -105,11 +201,22 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, float growth
 
 }  // namespace
 
+template <typename WT>
+static void adamw_launch(int clip, int grid, hipStream_t st, float* p, const float* g, float* m, float* v, WT* w, int64_t n, int64_t head, AdamArgs a,
+                         const float* amp, const float* lr_dev, const WT* g16, const float* clip_coef, float clip_value) {
+  if (clip == CLIP_COEF) hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_COEF>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value);
+  else if (clip == CLIP_VALUE) hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_VALUE>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value);
+  else hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_OFF>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value);
+}
+
 static int adamw_impl(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr, float beta1,
                       float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
-                      const float* amp_state, const float* lr_dev, dgtd_stream s) {
-  DGTD_PROF(s, DGTD_HBM, (w ? 30.0 : 28.0) * n - (g16 ? 2.0 * n : 0.0), "dgtd_adamw_flat[n=%lld%s]", (long long)n, g16 ? ",g16" : "");
+                      const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, dgtd_stream s) {
+  const int clip = clip_coef_dev ? CLIP_COEF : (clip_value > 0.f ? CLIP_VALUE : CLIP_OFF);
+  DGTD_PROF(s, DGTD_HBM, (w ? 30.0 : 28.0) * n - (g16 ? 2.0 * n : 0.0), "dgtd_adamw_flat[n=%lld%s%s]", (long long)n, g16 ? ",g16" : "",
+            clip == CLIP_COEF ? ",clip=norm" : (clip == CLIP_VALUE ? ",clip=value" : ""));
   DGTD_REQUIRE(n > 0 && p && (g || g16) && m && v, "adamw_flat: bad arguments");
+  DGTD_REQUIRE(!(clip_coef_dev && clip_value > 0.f), "adamw_flat: clip by norm (clip_coef_dev) and by value (clip_value > 0) exclude each other");
   if (!g) g = p;                                                             // never read; keeps the phase checks below trivially true
   DGTD_REQUIRE(!g16 || (DGTD_IS_HALF(w_dt) && ((uintptr_t)g16 % 8) * 2 == (uintptr_t)p % 16), "adamw_flat: the 16-bit gradient must share the phase of the masters");
   DGTD_REQUIRE(amp_state || (bias_correction1 > 0.f && bias_correction2 > 0.f), "adamw_flat: bias corrections must be positive");
@@ -121,8 +228,8 @@ static int adamw_impl(float* p, const float* g, const void* g16, float* m, float
   const int64_t head = std::min<int64_t>(n, ((16 - (int64_t)(ap % 16)) % 16) / 4);
   AdamArgs a{lr, beta1, beta2, eps, weight_decay, 1.f / bias_correction1, 1.f / sqrtf(bias_correction2), (float)log((double)beta1), (float)log((double)beta2)};
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((n + 3) / 4 + 8, 256), 8192));
-  if (w_dt == DGTD_F16) hipLaunchKernelGGL(adamw_flat_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, p, g, m, v, (f16_t*)w, n, head, a, amp_state, lr_dev, (const f16_t*)g16);
-  else hipLaunchKernelGGL(adamw_flat_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, p, g, m, v, (bf16_t*)w, n, head, a, amp_state, lr_dev, (const bf16_t*)g16);
+  if (w_dt == DGTD_F16) adamw_launch<f16_t>(clip, grid, (hipStream_t)s, p, g, m, v, (f16_t*)w, n, head, a, amp_state, lr_dev, (const f16_t*)g16, clip_coef_dev, clip_value);
+  else adamw_launch<bf16_t>(clip, grid, (hipStream_t)s, p, g, m, v, (bf16_t*)w, n, head, a, amp_state, lr_dev, (const bf16_t*)g16, clip_coef_dev, clip_value);
   DGTD_CHECK_LAUNCH("adamw_flat");
   return 0;
 }
@@ -131,20 +238,61 @@ extern "C" int dgtd_adamw_flat_amp(float* p, const float* g, float* m, float* v,
                                    float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
                                    const float* amp_state, const float* lr_dev, dgtd_stream s) {
   DGTD_REQUIRE(g, "adamw_flat: bad arguments");
-  return adamw_impl(p, g, nullptr, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, s);
+  return adamw_impl(p, g, nullptr, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, nullptr, 0.f, s);
 }
 
 extern "C" int dgtd_adamw_flat_g16(float* p, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr, float beta1,
                                    float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
                                    const float* amp_state, const float* lr_dev, dgtd_stream s) {
   DGTD_REQUIRE(g16, "adamw_flat_g16: bad arguments");
-  return adamw_impl(p, nullptr, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, s);
+  return adamw_impl(p, nullptr, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, nullptr, 0.f, s);
 }
 
 extern "C" int dgtd_adamw_flat(float* p, const float* g, float* m, float* v, void* w_bf16, int64_t n, float lr, float beta1, float beta2,
                                float eps, float weight_decay, float bias_correction1, float bias_correction2, dgtd_stream s) {
   return dgtd_adamw_flat_amp(p, g, m, v, w_bf16, DGTD_BF16, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2,
                              nullptr, nullptr, s);
+}
+
+extern "C" int dgtd_adamw_flat_clip(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
+                                    const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, dgtd_stream s) {
+  DGTD_REQUIRE((g != nullptr) != (g16 != nullptr), "adamw_flat_clip: exactly one of g (fp32) and g16 (16-bit payload) is given");
+  return adamw_impl(p, g, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev,
+                    clip_coef_dev, clip_value, s);
+}
+
+template <typename T>
+static void norm_partial_launch(int kind, int grid, hipStream_t st, const void* g, int64_t n, int64_t head, double* partial) {
+  if (kind == NORM_INF) hipLaunchKernelGGL((grad_norm_partial_kernel<T, NORM_INF>), dim3(grid), dim3(256), 0, st, (const T*)g, n, head, partial);
+  else hipLaunchKernelGGL((grad_norm_partial_kernel<T, NORM_L2>), dim3(grid), dim3(256), 0, st, (const T*)g, n, head, partial);
+}
+
+extern "C" int dgtd_grad_norm_partial(const void* g, dgtd_dtype dt, int64_t n, int kind, double* partial, int grid, dgtd_stream s) {
+  DGTD_PROF(s, DGTD_HBM, (dt == DGTD_F32 ? 4.0 : 2.0) * n, "dgtd_grad_norm_partial[n=%lld,%s]", (long long)n, kind == NORM_INF ? "inf" : "l2");
+  DGTD_REQUIRE(n > 0 && g && partial && grid >= 1 && grid <= 65535, "grad_norm_partial: bad arguments");
+  DGTD_REQUIRE(kind == NORM_L2 || kind == NORM_INF, "grad_norm_partial: kind is 0 (L2) or 1 (inf), got %d", kind);
+  DGTD_REQUIRE(dt == DGTD_F32 || DGTD_IS_HALF(dt), "grad_norm_partial: gradients are fp32, bf16 or fp16, got dtype %d", (int)dt);
+  const int64_t esz = dt == DGTD_F32 ? 4 : 2;
+  const uintptr_t ap = (uintptr_t)g;
+  DGTD_REQUIRE(ap % esz == 0 && (uintptr_t)partial % 8 == 0, "grad_norm_partial: g and partial must be aligned to their element size");
+  const int64_t head = std::min<int64_t>(n, ((16 - (int64_t)(ap % 16)) % 16) / esz);
+  if (dt == DGTD_BF16) norm_partial_launch<bf16_t>(kind, grid, (hipStream_t)s, g, n, head, partial);
+  else if (dt == DGTD_F16) norm_partial_launch<f16_t>(kind, grid, (hipStream_t)s, g, n, head, partial);
+  else norm_partial_launch<float>(kind, grid, (hipStream_t)s, g, n, head, partial);
+  DGTD_CHECK_LAUNCH("grad_norm_partial");
+  return 0;
+}
+
+extern "C" int dgtd_grad_clip_finalize(const double* partials, int64_t count, int kind, float max_norm, float* amp_state, float* clip_state,
+                                       dgtd_stream s) {
+  DGTD_PROF(s, DGTD_HBM, 8.0 * count, "dgtd_grad_clip_finalize[count=%lld]", (long long)count);
+  DGTD_REQUIRE(partials && count > 0 && clip_state && max_norm > 0.f, "grad_clip_finalize: bad arguments");
+  DGTD_REQUIRE(kind == NORM_L2 || kind == NORM_INF, "grad_clip_finalize: kind is 0 (L2) or 1 (inf), got %d", kind);
+  if (kind == NORM_INF) hipLaunchKernelGGL(grad_clip_finalize_kernel<NORM_INF>, dim3(1), dim3(1024), 0, (hipStream_t)s, partials, count, max_norm, amp_state, clip_state);
+  else hipLaunchKernelGGL(grad_clip_finalize_kernel<NORM_L2>, dim3(1), dim3(1024), 0, (hipStream_t)s, partials, count, max_norm, amp_state, clip_state);
+  DGTD_CHECK_LAUNCH("grad_clip_finalize");
+  return 0;
 }
 
 extern "C" int dgtd_found_inf(const float* g, int64_t n, float* found, dgtd_stream s) {

@@ -1,6 +1,6 @@
 """Minimal config-driven runner for the keys the reference's YAML files use (config/sod.yml:1-104, config/cod.yml:1-143):
 ``train_cfg`` (by_epoch, max_epochs, val_interval), ``train_dataloader.batch_size``, ``model.type`` (+ kwargs the reference
-ignores, cod.py:38-46), ``optim_wrapper`` (AdamW, ``paramwise_cfg.custom_keys`` lr_mult, bypass_duplicate),
+ignores, cod.py:38-46), ``optim_wrapper`` (AdamW, ``paramwise_cfg.custom_keys`` lr_mult, bypass_duplicate, ``clip_grad`` by norm or by value),
 ``param_scheduler`` (CosineAnnealingLR by epoch), ``default_hooks.logger.interval`` / ``checkpoint.interval``,
 ``custom_hooks: our_init``, ``*_dataloader.sampler`` (DefaultSampler), ``val_evaluator``, ``optim_wrapper.type: AmpOptimWrapper``
 (= fp16 autocast + dynamic loss scaling when the runner is built with ``compute_dtype=torch.float16``).  The external nest/mmengine runner is out of scope; this is what drives the HIP-backed model from
@@ -17,7 +17,7 @@ import yaml
 from .checkpoint import load_checkpoint_file, load_pretrained, save_checkpoint
 from .data import DefaultSampler, batches
 from .metrics import build_evaluators
-from .optim import FlatAdamW, LossScaler, build_optimizer
+from .optim import FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, parse_clip_grad
 
 MODEL_REGISTRY: Dict[str, Callable] = {}
 
@@ -105,12 +105,15 @@ class Runner:
         assert ocfg.get("type") == "AdamW", "the reference configs use AdamW (config/sod.yml:58-61)"
         on_gpu = torch.device(device).type == "cuda"
         self.scaler = None
+        # optim_wrapper.clip_grad (config/cod.yml:108-110): inside FlatAdamW on the HIP device, torch's utilities before torch.optim.AdamW on CPU
+        self.clip_grad = parse_clip_grad(ow.get("clip_grad"))
+        self._grad_norm = None
         if on_gpu:
             if compute_dtype == torch.float16:
                 assert ow.get("type") == "AmpOptimWrapper", "fp16 compute needs the AmpOptimWrapper recipe (loss scaling)"
                 self.scaler = LossScaler(device)
             self.optimizer = FlatAdamW(self.reducer, lr=float(ocfg["lr"]), weight_decay=float(ocfg.get("weight_decay", 0.0)),
-                                       custom_keys=custom_keys_of(cfg), scaler=self.scaler)
+                                       custom_keys=custom_keys_of(cfg), scaler=self.scaler, clip_grad=self.clip_grad)
         else:
             self.optimizer = build_optim(cfg, self.model)
         tc = cfg["train_cfg"]
@@ -142,10 +145,18 @@ class Runner:
         loss = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="loss")["loss"]
         (self.scaler.scale(loss) if self.scaler is not None else loss).backward()
         self.reducer.finish()
+        if self.clip_grad is not None and not isinstance(self.optimizer, FlatAdamW):
+            self._grad_norm = clip_grad_torch((p for g in self.optimizer.param_groups for p in g["params"]), self.clip_grad)
         self.optimizer.step()
         if not isinstance(self.optimizer, FlatAdamW):
             self.reducer.refresh_working()
         return loss
+
+    def grad_norm(self):
+        """Clip by norm: the total gradient norm of the last step (a host read on the HIP device); ``None`` otherwise."""
+        if isinstance(self.optimizer, FlatAdamW):
+            return self.optimizer.grad_norm()
+        return None if self._grad_norm is None else float(self._grad_norm)
 
     def train(self, loader_fn: Callable[[int], Iterable[dict]], epochs: Optional[int] = None, val_loader_fn: Optional[Callable[[], Iterable[dict]]] = None):
         """Epochs ``self.epoch .. (epochs or max_epochs)``: the loop the reference gets from mmengine's EpochBasedTrainLoop
@@ -157,7 +168,10 @@ class Runner:
                 loss = self.train_step(batch)
                 losses.append(loss.detach())
                 if (it + 1) % self.log_interval == 0:
-                    self.log(f"epoch {epoch + 1} iter {it + 1} loss {loss.item():.4f} lr {self.optimizer.param_groups[0]['lr']:.3e}")
+                    line = f"epoch {epoch + 1} iter {it + 1} loss {loss.item():.4f} lr {self.optimizer.param_groups[0]['lr']:.3e}"
+                    if self.clip_grad is not None and self.clip_grad["type"] == "norm":      # mmengine logs it too; read only here
+                        line += f" grad_norm {self.grad_norm():.4f}"
+                    self.log(line)
             if self.scheduler is not None:
                 self.scheduler.step()
             self.epoch = epoch + 1

@@ -3,8 +3,9 @@ mmengine's ``paramwise_cfg.custom_keys`` semantics = the LONGEST matching substr
 ``bypass_duplicate`` = a parameter reachable under several names (the shared PReLU) is added once."""
 from __future__ import annotations
 
+import math
 import os
-from typing import Dict, Optional
+from typing import Dict, Iterable, Optional
 
 import torch
 
@@ -42,6 +43,53 @@ def build_optimizer(model: torch.nn.Module, lr: float = 5e-4, weight_decay: floa
         fused = any(p.is_cuda for g in param_groups for p in g["params"])
     return torch.optim.AdamW(param_groups, lr=lr, weight_decay=weight_decay, fused=fused, capturable=capturable and fused)
 
+
+def parse_clip_grad(clip_grad: Optional[dict]) -> Optional[dict]:
+    """``optim_wrapper.clip_grad`` in mmengine's spellings (OptimWrapper, config/cod.yml:108-110) -> a normal form, or ValueError:
+    ``{"max_norm": x, "norm_type": 2 | "inf"}`` (optionally ``"type": "norm"``) -> ``{"type": "norm", "max_norm": x, "norm_type": 2.0 | inf}``;
+    ``{"type": "value", "clip_value": x}`` -> ``{"type": "value", "clip_value": x}``; ``None`` (key absent) -> ``None``."""
+    if clip_grad is None:
+        return None
+    if not isinstance(clip_grad, dict) or not clip_grad:
+        raise ValueError(f"clip_grad must be a non-empty dict, got {clip_grad!r}")
+    kind = clip_grad.get("type", "norm")
+    if kind not in ("norm", "value"):
+        raise ValueError(f"clip_grad.type must be 'norm' or 'value', got {kind!r}")
+    if "max_norm" in clip_grad and "clip_value" in clip_grad:
+        raise ValueError("clip_grad: max_norm (clip by norm) and clip_value (clip by value) exclude each other")
+    allowed = {"type", "max_norm", "norm_type"} if kind == "norm" else {"type", "clip_value"}
+    extra = set(clip_grad) - allowed
+    if extra:
+        raise ValueError(f"clip_grad of type {kind!r} does not take {sorted(extra)}")
+    key = "max_norm" if kind == "norm" else "clip_value"
+    if key not in clip_grad:
+        raise ValueError(f"clip_grad of type {kind!r} needs {key}")
+
+    def bound(v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v > 0) or math.isinf(v):
+            raise ValueError(f"clip_grad.{key} must be a positive finite number, got {v!r}")
+        return float(v)
+    if kind == "value":
+        return {"type": "value", "clip_value": bound(clip_grad["clip_value"])}
+    nt = clip_grad.get("norm_type", 2)
+    if isinstance(nt, str):
+        nt = math.inf if nt == "inf" else None
+    if isinstance(nt, bool) or not isinstance(nt, (int, float)) or float(nt) not in (2.0, math.inf):
+        raise ValueError(f"clip_grad.norm_type must be 2 or 'inf', got {clip_grad.get('norm_type')!r}")
+    return {"type": "norm", "max_norm": bound(clip_grad["max_norm"]), "norm_type": float(nt)}
+
+
+def clip_grad_torch(params: Iterable[torch.Tensor], clip_grad: Optional[dict]) -> Optional[torch.Tensor]:
+    """The CPU path (torch.optim.AdamW): ``clip_grad`` applied with torch's own utilities to the parameters that have a gradient.
+    Returns the total norm (clip by norm) or ``None``."""
+    cg = parse_clip_grad(clip_grad)
+    if cg is None:
+        return None
+    params = [p for p in params if p.grad is not None]
+    if cg["type"] == "norm":
+        return torch.nn.utils.clip_grad_norm_(params, cg["max_norm"], norm_type=cg["norm_type"])
+    torch.nn.utils.clip_grad_value_(params, cg["clip_value"])
+    return None
 
 
 class LossScaler:
@@ -83,12 +131,23 @@ class FlatAdamW:
     ``scaler``: a ``LossScaler`` (fp16 mode): the gradients are checked for inf / NaN (one pass per bucket), un-scaled inside
     the AdamW launch, and an overflowed step is skipped on the device.
     ``state_dict()`` has torch.optim.AdamW's layout (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` in the parameters'
-    logical shapes, ``param_groups`` with parameter indices, plus ``param_names``), whatever the bucket size was."""
+    logical shapes, ``param_groups`` with parameter indices, plus ``param_names``), whatever the bucket size was.
+    ``clip_grad``: mmengine's ``optim_wrapper.clip_grad`` (see ``parse_clip_grad``), on the device and capturable.
+    Clip by norm: one ``dgtd_grad_norm_partial`` launch per run AdamW will update, over the operand AdamW will read (the 16-bit payload
+    where the direct path applies, the fp32 bucket elsewhere; slots without a gradient and the alignment padding are zero), one
+    ``dgtd_grad_clip_finalize`` that leaves { total norm, coefficient } in device memory, then the AdamW launches, which multiply by the
+    coefficient.  With a ``scaler`` the norm pass IS the inf / NaN check (the finalize raises ``found_inf``): ``dgtd_found_inf`` is not
+    launched.  A global norm needs every bucket: under ``pipelined`` each bucket's norm launch still waits for that bucket's all-reduce
+    only, but the finalize and with it every AdamW launch come after the last bucket, so AdamW of the first buckets no longer overlaps
+    the later all-reduces.  All-reduced gradients are identical on every rank, so the norm needs no collective of its own.
+    Clip by value: only an argument of the AdamW launches changes."""
 
     def __init__(self, reducer, lr: float = 5e-4, weight_decay: float = 0.1, betas=(0.9, 0.999), eps: float = 1e-8,
-                 custom_keys: Optional[Dict[str, float]] = None, scaler: Optional[LossScaler] = None, graph_safe: bool = False):
+                 custom_keys: Optional[Dict[str, float]] = None, scaler: Optional[LossScaler] = None, graph_safe: bool = False,
+                 clip_grad: Optional[dict] = None):
         from .. import _lib as L
         self._L = L
+        self.clip_grad = parse_clip_grad(clip_grad)      # ValueError before anything is built
         self.reducer, self.scaler = reducer, scaler
         custom_keys = SOD_CUSTOM_KEYS if custom_keys is None else custom_keys
         self.betas, self.eps, self.weight_decay, self._steps = betas, eps, weight_decay, 0
@@ -116,6 +175,24 @@ class FlatAdamW:
             torch.tensor([1.0, 0.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=dev) if graph_safe else None)
         self._lr_dev = torch.tensor([g["lr"] for g in self.param_groups], dtype=torch.float32, device=dev) if graph_safe else None
         self._lr_host = [g["lr"] for g in self.param_groups]
+        # clip by norm: { total norm, coefficient } and the fp64 partials (one per workgroup of every norm launch) live in device memory,
+        # allocated once.  Runs are unions of whole slots and _norm_grid is subadditive, so the per-slot sum bounds every step's need.
+        self._clip_norm = self.clip_grad is not None and self.clip_grad["type"] == "norm"
+        self._clip_value = self.clip_grad["clip_value"] if (self.clip_grad is not None and not self._clip_norm) else 0.0
+        self._clip_state = self._norm_ws = None
+        if self._clip_norm:
+            self._clip_state = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._norm_ws = torch.zeros(max(1, sum(self._norm_grid(n) for slots in self.slots for _, n, _ in slots)), dtype=torch.float64, device=dev)
+            self._norm_kind = 1 if math.isinf(self.clip_grad["norm_type"]) else 0
+
+    @staticmethod
+    def _norm_grid(n: int) -> int:
+        """Workgroups of one norm launch: 4096 elements each, at most 1024 (4 workgroups per CU keep ~64 KB of loads in flight per CU)."""
+        return max(1, min(1024, -(-n // 4096)))
+
+    def grad_norm(self) -> Optional[float]:
+        """Clip by norm: the un-scaled total gradient norm of the last step (ONE host read); ``None`` otherwise."""
+        return float(self._clip_state[0].item()) if self._clip_norm else None
 
     @property
     def steps(self) -> int:
@@ -148,6 +225,20 @@ class FlatAdamW:
     def zero_grad(self, set_to_none: bool = True) -> None:
         self.reducer.zero_grad()
 
+    def _join(self, b, slots, runs):
+        """Wait for bucket ``b``'s all-reduce (pipelined) and settle what this step reads and updates: (16-bit payload or None, runs)."""
+        # pipelined: the bucket's all-reduce runs on the reducer's side stream and is joined bucket by bucket; without a loss scaler
+        # (no found_inf pass over the fp32 bucket) the working-copy segment is updated straight from the 16-bit payload
+        g16 = b.get("g16") if (self.pipelined and self.scaler is None and b.get("works") and _ADAM_G16) else None
+        if self.pipelined:
+            self.reducer.wait_bucket(b["index"], widen=g16 is None)
+        # world 1: parameters without a gradient this step are skipped, like torch.optim.AdamW does.  N > 1: ``missing`` is
+        # rank-local while the all-reduced slot holds the average over every rank (zero from the ranks that did not use the
+        # parameter) - every rank applies the same update, so the replicas cannot drift apart (ADVICE r2)
+        if b["missing"] and self.reducer.world == 1:
+            runs = self._merge(slots, b["n_work"], set(b["missing"]))
+        return g16, runs
+
     @torch.no_grad()
     def step(self) -> None:
         L = self._L
@@ -156,32 +247,46 @@ class FlatAdamW:
         bc1, bc2 = 1.0 - b1 ** self._steps, 1.0 - b2 ** self._steps
         st = L.stream_ptr()
         amp = self._state.data_ptr() if self._state is not None else None
-        if self.scaler is not None:
+        if self.scaler is not None and not self._clip_norm:
             for b in self.reducer.buckets:          # GradScaler.unscale_'s found_inf over every (already all-reduced) gradient
                 if self.pipelined:
                     self.reducer.wait_bucket(b["index"])
                 L.call("dgtd_found_inf", b["flat"].data_ptr(), b["flat"].numel(), amp + 12, st)
         lrp = self._lr_dev.data_ptr() if self._lr_dev is not None else None
-        for b, slots, runs, state in zip(self.reducer.buckets, self.slots, self.runs, self.state):
-            # pipelined: the bucket's all-reduce runs on the reducer's side stream and is joined bucket by bucket; without a loss scaler
-            # (no found_inf pass over the fp32 bucket) the working-copy segment is updated straight from the 16-bit payload
-            g16 = b.get("g16") if (self.pipelined and self.scaler is None and b.get("works") and _ADAM_G16) else None
-            if self.pipelined:
-                self.reducer.wait_bucket(b["index"], widen=g16 is None)
+        plans = None
+        if self._clip_norm:
+            # every bucket's partial sums (joining that bucket's all-reduce only), then ONE finalize: nothing below starts before it
+            plans, k, ws = [], 0, self._norm_ws
+            for b, slots, runs in zip(self.reducer.buckets, self.slots, self.runs):
+                g16, runs = self._join(b, slots, runs)
+                plans.append((g16, runs))
+                for lo, hi, _ in runs:
+                    direct = g16 is not None and hi <= b["n_work"]
+                    grid = self._norm_grid(hi - lo)
+                    assert k + grid <= ws.numel()
+                    L.call("dgtd_grad_norm_partial", (g16.data_ptr() + 2 * lo) if direct else (b["flat"].data_ptr() + 4 * lo),
+                           self._w_dt if direct else L.F32, hi - lo, self._norm_kind, ws.data_ptr() + 8 * k, grid, st)
+                    k += grid
+            if k:
+                L.call("dgtd_grad_clip_finalize", ws.data_ptr(), k, self._norm_kind, self.clip_grad["max_norm"],
+                       amp if self.scaler is not None else None, self._clip_state.data_ptr(), st)
+        coef = (self._clip_state.data_ptr() + 4) if self._clip_norm else None
+        for i, (b, slots, runs, state) in enumerate(zip(self.reducer.buckets, self.slots, self.runs, self.state)):
+            g16, runs = plans[i] if plans is not None else self._join(b, slots, runs)
             p, g, m, v, w, nw = b["mflat"], b["flat"], state["exp_avg"], state["exp_avg_sq"], b["wflat"], b["n_work"]
-            # world 1: parameters without a gradient this step are skipped, like torch.optim.AdamW does.  N > 1: ``missing`` is
-            # rank-local while the all-reduced slot holds the average over every rank (zero from the ranks that did not use the
-            # parameter) - every rank applies the same update, so the replicas cannot drift apart
-            if b["missing"] and self.reducer.world == 1:
-                runs = self._merge(slots, nw, set(b["missing"]))
             for lo, hi, gi in runs:
                 wp = (w.data_ptr() + 2 * lo) if (w is not None and hi <= nw) else None
                 direct = g16 is not None and hi <= nw
-                L.call("dgtd_adamw_flat_g16" if direct else "dgtd_adamw_flat_amp", p.data_ptr() + 4 * lo,
-                       (g16.data_ptr() + 2 * lo) if direct else (g.data_ptr() + 4 * lo), m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, wp,
-                       self._w_dt, hi - lo, float(self.param_groups[gi]["lr"]), b1, b2, self.eps,
-                       float(self.param_groups[gi]["weight_decay"]), bc1, bc2, amp,
-                       (lrp + 4 * gi) if lrp is not None else None, st)
+                tail = (m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, wp,
+                        self._w_dt, hi - lo, float(self.param_groups[gi]["lr"]), b1, b2, self.eps,
+                        float(self.param_groups[gi]["weight_decay"]), bc1, bc2, amp,
+                        (lrp + 4 * gi) if lrp is not None else None)
+                if self.clip_grad is None:
+                    L.call("dgtd_adamw_flat_g16" if direct else "dgtd_adamw_flat_amp", p.data_ptr() + 4 * lo,
+                           (g16.data_ptr() + 2 * lo) if direct else (g.data_ptr() + 4 * lo), *tail, st)
+                else:
+                    L.call("dgtd_adamw_flat_clip", p.data_ptr() + 4 * lo, None if direct else (g.data_ptr() + 4 * lo),
+                           (g16.data_ptr() + 2 * lo) if direct else None, *tail, coef, self._clip_value, st)
         if self.scaler is not None:
             L.call("dgtd_loss_scale_update", self.scaler.state.data_ptr(), float(self.scaler.growth_factor),
                    float(self.scaler.backoff_factor), int(self.scaler.growth_interval), st)

@@ -370,6 +370,27 @@ int dgtd_adamw_flat_amp(float* p, const float* g, float* m, float* v, void* w, d
 int dgtd_adamw_flat_g16(float* p, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr, float beta1,
                         float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
                         const float* amp_state, const float* lr_dev, dgtd_stream s);
+/* The same update with gradient clipping (mmengine's optim_wrapper.clip_grad).  Exactly one of g (fp32 bucket) and g16 (16-bit payload,
+ * dtype w_dt) is given.  clip_coef_dev (device scalar or NULL): the effective gradient is g * 1/scale * (*clip_coef_dev), the
+ * coefficient dgtd_grad_clip_finalize wrote (clip by global norm).  clip_value > 0: the effective gradient is g * 1/scale clamped to
+ * +-clip_value, a NaN passing through as with torch's clamp_ (clip by value); <= 0: off.  Both at once is an argument error; with
+ * neither this is dgtd_adamw_flat_amp / dgtd_adamw_flat_g16 bit for bit.                                                            */
+int dgtd_adamw_flat_clip(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
+                         const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, dgtd_stream s);
+/* ---- Global gradient norm for clip_grad: partials per run, then one finalize ----
+ * dgtd_grad_norm_partial: g [n] (dt = DGTD_F32, DGTD_BF16 or DGTD_F16, any element-aligned start) -> partial [grid] fp64, one value per
+ * workgroup: kind 0 (L2) = sum of g^2 with every element widened to fp64 before it is squared (no overflow; non-finite iff an element
+ * is), kind 1 (inf) = max |g|, NaN if an element is NaN.  `grid` workgroups of 256 threads (1..65535), chosen by the caller, who owns
+ * partial.  Fixed reduction order and no atomics: the result is bit-reproducible for a given (n, alignment, grid).                  */
+int dgtd_grad_norm_partial(const void* g, dgtd_dtype dt, int64_t n, int kind, double* partial, int grid, dgtd_stream s);
+/* dgtd_grad_clip_finalize: one workgroup reduces partials [count] (every run of every bucket, in index order) in fp64, takes the square
+ * root (L2), multiplies by amp_state[2] = 1/scale when amp_state (layout above) is given, rounds ONCE to fp32 and writes clip_state
+ * (device, fp32 [2]) = { total_norm, clip_coef = min(1, max_norm / (total_norm + 1e-6)) } (torch.nn.utils.clip_grad_norm_).  A
+ * non-finite reduced value sets amp_state[3] = 1: the found_inf of the step, so dgtd_found_inf is not needed beside it.  Without
+ * amp_state a non-finite norm gives a NaN coefficient, as torch does.                                                               */
+int dgtd_grad_clip_finalize(const double* partials, int64_t count, int kind, float max_norm, float* amp_state, float* clip_state,
+                            dgtd_stream s);
 /* found[0] = 1 when g[0,n) (fp32, the still scaled gradients) holds an inf or a NaN; untouched otherwise.                        */
 int dgtd_found_inf(const float* g, int64_t n, float* found, dgtd_stream s);
 /* GradScaler.update() on the device: state fp32 [5] (layout above); found_inf != 0: scale *= backoff, tracker = 0; else steps += 1,
