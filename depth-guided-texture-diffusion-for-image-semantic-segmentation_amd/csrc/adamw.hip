@@ -228,8 +228,7 @@ static int adamw_impl(float* p, const float* g, const void* g16, float* m, float
   const int64_t head = std::min<int64_t>(n, ((16 - (int64_t)(ap % 16)) % 16) / 4);
   AdamArgs a{lr, beta1, beta2, eps, weight_decay, 1.f / bias_correction1, 1.f / sqrtf(bias_correction2), (float)log((double)beta1), (float)log((double)beta2)};
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((n + 3) / 4 + 8, 256), 8192));
-  if (w_dt == DGTD_F16) adamw_launch<f16_t>(clip, grid, (hipStream_t)s, p, g, m, v, (f16_t*)w, n, head, a, amp_state, lr_dev, (const f16_t*)g16, clip_coef_dev, clip_value);
-  else adamw_launch<bf16_t>(clip, grid, (hipStream_t)s, p, g, m, v, (bf16_t*)w, n, head, a, amp_state, lr_dev, (const bf16_t*)g16, clip_coef_dev, clip_value);
+  DGTD_DISPATCH_HALF(w_dt, adamw_launch<T_>(clip, grid, (hipStream_t)s, p, g, m, v, (T_*)w, n, head, a, amp_state, lr_dev, (const T_*)g16, clip_coef_dev, clip_value));
   DGTD_CHECK_LAUNCH("adamw_flat");
   return 0;
 }
@@ -277,9 +276,7 @@ extern "C" int dgtd_grad_norm_partial(const void* g, dgtd_dtype dt, int64_t n, i
   const uintptr_t ap = (uintptr_t)g;
   DGTD_REQUIRE(ap % esz == 0 && (uintptr_t)partial % 8 == 0, "grad_norm_partial: g and partial must be aligned to their element size");
   const int64_t head = std::min<int64_t>(n, ((16 - (int64_t)(ap % 16)) % 16) / esz);
-  if (dt == DGTD_BF16) norm_partial_launch<bf16_t>(kind, grid, (hipStream_t)s, g, n, head, partial);
-  else if (dt == DGTD_F16) norm_partial_launch<f16_t>(kind, grid, (hipStream_t)s, g, n, head, partial);
-  else norm_partial_launch<float>(kind, grid, (hipStream_t)s, g, n, head, partial);
+  DGTD_DISPATCH(dt, norm_partial_launch<T_>(kind, grid, (hipStream_t)s, g, n, head, partial));
   DGTD_CHECK_LAUNCH("grad_norm_partial");
   return 0;
 }

@@ -554,7 +554,7 @@ extern "C" int dgtd_sra_attn_bwd(const void* q, const void* kv, const void* out,
     // writes a plain partial slab and ONE reduce launch sums them (was: fp32 atomics into a caller-zeroed buffer).
     const int kgroups = (int)cdiv(Nkv, KGROUP);
     DGTD_REQUIRE((int64_t)heads * kgroups <= 65535, "sra_attn_bwd: heads*kgroups too large for the grid");
-    static const int64_t wg_env = getenv("DGTD_DKDV_WGS") ? atol(getenv("DGTD_DKDV_WGS")) : 0;
+    static const int64_t wg_env = env_int("DGTD_DKDV_WGS", 0);
     const int64_t cols = (int64_t)B * heads * kgroups;
     const int64_t wg_target = wg_env ? std::min<int64_t>(wg_env, DKDV_MAX_WGS) : (cols <= 32 ? 512 : 256);
     int nq = (int)std::min<int64_t>(qtiles, std::max<int64_t>(1, cdiv(wg_target, cols)));

@@ -196,14 +196,11 @@ extern "C" int dgtd_batchnorm_fwd(const void* x, const float* gamma, const float
   const hipStream_t st = (hipStream_t)s;
   const int V = DGTD_IS_HALF(dt) ? 8 : 4, rpp = 256 / (C / V), P = training ? slices_for(N, rpp) : 0, grid = apply_grid(N * (C / V));
   if (training) {
-    if (dt == DGTD_F16) hipLaunchKernelGGL((bn_partial_kernel<f16_t, 0>), dim3(P), dim3(256), 0, st, (const f16_t*)x, (const f16_t*)nullptr, (const float*)nullptr, scratch, N, C);
-    else if (dt == DGTD_BF16) hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 0>), dim3(P), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (const float*)nullptr, scratch, N, C);
-    else hipLaunchKernelGGL((bn_partial_kernel<float, 0>), dim3(P), dim3(256), 0, st, (const float*)x, (const float*)nullptr, (const float*)nullptr, scratch, N, C);
+    DGTD_DISPATCH(dt, hipLaunchKernelGGL((bn_partial_kernel<T_, 0>), dim3(P), dim3(256), 0, st, (const T_*)x, (const T_*)nullptr, (const float*)nullptr, scratch, N, C));
     DGTD_CHECK_LAUNCH("bn_partial");
   }
-  if (dt == DGTD_F16) hipLaunchKernelGGL(bn_apply_kernel<f16_t>, dim3(grid), dim3(256), 0, st, (const f16_t*)x, (const float*)scratch, P, rpp, gamma, beta, running_mean, running_var, num_batches, (f16_t*)y, save, N, C, eps, momentum);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const float*)scratch, P, rpp, gamma, beta, running_mean, running_var, num_batches, (bf16_t*)y, save, N, C, eps, momentum);
-  else hipLaunchKernelGGL(bn_apply_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (const float*)scratch, P, rpp, gamma, beta, running_mean, running_var, num_batches, (float*)y, save, N, C, eps, momentum);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(bn_apply_kernel<T_>, dim3(grid), dim3(256), 0, st, (const T_*)x, (const float*)scratch, P, rpp, gamma, beta, running_mean, running_var,
+                                       num_batches, (T_*)y, save, N, C, eps, momentum));
   DGTD_CHECK_LAUNCH("bn_apply");
   return 0;
 }
@@ -215,13 +212,10 @@ extern "C" int dgtd_batchnorm_bwd(const void* dy, const void* x, const float* ga
   DGTD_REQUIRE(save && scratch, "batchnorm_bwd: needs the saved statistics and scratch");
   const hipStream_t st = (hipStream_t)s;
   const int V = DGTD_IS_HALF(dt) ? 8 : 4, rpp = 256 / (C / V), P = slices_for(N, rpp), grid = apply_grid(N * (C / V));
-  if (dt == DGTD_F16) hipLaunchKernelGGL((bn_partial_kernel<f16_t, 1>), dim3(P), dim3(256), 0, st, (const f16_t*)dy, (const f16_t*)x, save, scratch, N, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL((bn_partial_kernel<bf16_t, 1>), dim3(P), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, save, scratch, N, C);
-  else hipLaunchKernelGGL((bn_partial_kernel<float, 1>), dim3(P), dim3(256), 0, st, (const float*)dy, (const float*)x, save, scratch, N, C);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL((bn_partial_kernel<T_, 1>), dim3(P), dim3(256), 0, st, (const T_*)dy, (const T_*)x, save, scratch, N, C));
   DGTD_CHECK_LAUNCH("bn_bwd_partial");
-  if (dt == DGTD_F16) hipLaunchKernelGGL(bn_bwd_apply_kernel<f16_t>, dim3(grid), dim3(256), 0, st, (const f16_t*)dy, (const f16_t*)x, (const float*)scratch, P, gamma, save, (f16_t*)dx, dgamma, dbeta, N, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)scratch, P, gamma, save, (bf16_t*)dx, dgamma, dbeta, N, C);
-  else hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)scratch, P, gamma, save, (float*)dx, dgamma, dbeta, N, C);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(bn_bwd_apply_kernel<T_>, dim3(grid), dim3(256), 0, st, (const T_*)dy, (const T_*)x, (const float*)scratch, P, gamma, save, (T_*)dx,
+                                       dgamma, dbeta, N, C));
   DGTD_CHECK_LAUNCH("bn_bwd_apply");
   return 0;
 }

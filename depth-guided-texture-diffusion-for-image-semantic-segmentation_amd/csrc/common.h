@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/dgtd.h"
 
 typedef __bf16 bf16_t;
@@ -52,6 +53,11 @@ template <> struct Vec16<f16_t> { static constexpr int N = 8; typedef f16x8 type
 template <typename T> struct Vec8;
 template <> struct Vec8<bf16_t> { typedef bf16x4 type; };
 template <> struct Vec8<f16_t> { typedef f16x4 type; };
+// two adjacent elements of T (one 4-byte load of a 16-bit type, 8 bytes of fp32): a lane's channel pair in the depthwise kernels
+template <typename T> struct Vec2;
+template <> struct Vec2<float> { typedef float type __attribute__((ext_vector_type(2))); };
+template <> struct Vec2<bf16_t> { typedef bf16_t type __attribute__((ext_vector_type(2))); };
+template <> struct Vec2<f16_t> { typedef f16_t type __attribute__((ext_vector_type(2))); };
 
 // the 16-bit MFMA of the I/O type: v_mfma_f32_32x32x16_bf16 / v_mfma_f32_32x32x16_f16 (same shape, same cycles)
 __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
@@ -64,6 +70,11 @@ __device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __
                                      else { typedef float T_; STMT; } } while (0)
 // same for the 16-bit types only (callers have checked DGTD_IS_HALF)
 #define DGTD_DISPATCH_HALF(dt, STMT) do { if ((dt) == DGTD_F16) { typedef f16_t T_; STMT; } else { typedef bf16_t T_; STMT; } } while (0)
+// run STMT with K_ bound to the depthwise filter size (callers have checked K == 3 || K == 7)
+#define DGTD_DISPATCH_K37(K, STMT) do { if ((K) == 7) { constexpr int K_ = 7; STMT; } else { constexpr int K_ = 3; STMT; } } while (0)
+
+// launch-geometry knobs (the tools/*_sweep.sh scripts drive them): read once, into a function-local `static const`
+static inline long env_int(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

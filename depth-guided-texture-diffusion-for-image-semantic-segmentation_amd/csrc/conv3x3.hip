@@ -431,8 +431,7 @@ int dispatch_fwd_geom(const void* x, const void* mask, const void* w, const void
   const FwdGeom g = fwd_geom(Z, B, H, W, CI);
   if constexpr (NT > 1) {   // fewer than 2 workgroups per CU: one workgroup per 32-channel output tile
     const long wgs = (long)Z * B * cdiv(H, 4 * (32 / g.twx)) * cdiv(W, g.twx);
-    static const bool split_on = !(getenv("DGTD_CONV3X3_SPLIT") && getenv("DGTD_CONV3X3_SPLIT")[0] == '0');
-    if (split_on && wgs < 512) {
+    if (wgs < 512) {
       if (g.twx == 16) return launch_fwd<T, CI, 1, 1, 16>(x, mask, w, bias, y, Z, B, H, W, Co, relu, shared_x, st, epi, NT);
       return launch_fwd<T, CI, 1, 1, 32>(x, mask, w, bias, y, Z, B, H, W, Co, relu, shared_x, st, epi, NT);
     }
@@ -508,7 +507,7 @@ inline int wgrad_splits(int Z, int B, int H, int W, int Ci, int Co) {
   const long ygroups = (long)Z * cdiv(Co, 32) * (Ci > 32 ? 3 : 1);
   // ~2 workgroups per CU; 96 -> 96 channels (9 output tiles x 3 filter-row groups per pixel split) runs better with ~4 (measured:
   // 16 convolutions at 64x64 343 -> 304 us; every other geometry of the model is slower with more partial sums)
-  static const long wgs_env = getenv("DGTD_WGRAD_WGS") ? atol(getenv("DGTD_WGRAD_WGS")) : 0;
+  static const long wgs_env = env_int("DGTD_WGRAD_WGS", 0);
   const long wgs = wgs_env ? wgs_env : (Ci >= 96 && Co >= 96 ? 1024 : 512);
   const long want = std::max<long>(1, wgs / ygroups);
   // the partial sums written (and re-read by the reduce kernel) should stay below the bytes of the two input maps

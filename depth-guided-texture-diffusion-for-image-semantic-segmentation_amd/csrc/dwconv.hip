@@ -8,31 +8,23 @@
 //   7x7 forward / input gradient: LDS-tiled kernels (dwconv_tiled.hip); direct strip kernel kept for C % 128 != 0.
 //   3x3 forward / input gradient: sliding window (dwconv3_sw_kernel) - a thread owns 4 x-positions x 4 channels and walks down the
 //     image with the three input rows in registers, every row loaded once; modes fuse bias, GELU, GELU' and the skip-gradient add.
-//   weight gradient, one layer per launch: K waves per workgroup = the K filter rows of a strip column, per-workgroup partial rows,
-//     fixed-order second stage (no atomics anywhere).
+//     The direct strip kernel serves H < 8 and C % 4 != 0.  Which kernel runs is decided by the shape alone.
+//   weight gradient, one layer per launch (dwconv_bwd_weight_kernel): K waves per workgroup = the K filter rows of a strip column,
+//     per-workgroup partial rows, fixed-order second stage (no atomics anywhere).  dgtd_dwconv_bwd_weight_workspace is the size of
+//     exactly those partial rows, which is what dgtd_dwconv_bwd_weight and dgtd_dwconv_bwd_weight_partial write.
 //   weight gradient, all same-shaped layers of the step in one launch (deferred phase): dwconv_bww_sw_kernel - one wave
 //     owns all K filter rows of a strip and slides down the image, gradient rows in a register window.
 //   weights are packed to fp32 tap-major (+ spatially flipped copy + bias) once per step for all layers (dwconv_pack_batched).
 // bwd-data is the forward kernel with the spatially flipped filter.
 #include "common.h"
-#include <stdlib.h>
 
-// LDS-tiled variants (dwconv_tiled.hip), used whenever C % 128 == 0; DGTD_DWCONV_TILED=0 selects the direct kernels for A/B runs
+// LDS-tiled 7x7 forward (dwconv_tiled.hip), used whenever C % 128 == 0
 int dgtd_dwconv_tiled_fwd(const void* x, const float* wt, const float* bias, const void* aux, void* y, int B, int H, int W, int C, int K,
                           int mode, dgtd_dtype dt, hipStream_t s);
-int dgtd_dwconv_tiled_bww(const void* x, const void* du, float* grads, int has_bias, void* workspace, int B, int H, int W, int C, int K,
-                          dgtd_dtype dt, hipStream_t s);
-int dgtd_dwconv_tiled_bww_groups(int B, int H, int W, int C);
-static bool use_tiled() {
-  static const bool on = [] { const char* e = getenv("DGTD_DWCONV_TILED"); return !(e && e[0] == '0'); }();
-  return on;
-}
 
 namespace {
 
-__device__ __forceinline__ float gelu_f(float x) { return gelu_fast(x); }        // common.h: erfc by A&S 7.1.26, |Phi error| <= 5e-7
-__device__ __forceinline__ float gelu_grad_f(float x) { return gelu_grad_fast(x); }
-
+// GELU: gelu_fast / gelu_grad_fast of common.h (erfc by A&S 7.1.26, |Phi error| <= 5e-7)
 // MODE 0: y = conv(x) + bias          MODE 1: y = gelu(conv(x) + bias)
 // MODE 2: y = aux * gelu'(conv(x) + bias)   (aux = upstream gradient; recomputes the pre-activation)
 // MODE 3: y = conv(x) + bias + aux          (backward w.r.t. x of a residual block: aux = gradient of the skip branch)
@@ -116,14 +108,14 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const T* __restrict__ x
         if (MODE == 2) {
           VT g = *reinterpret_cast<const VT*>(aux + (((size_t)b * H + yy0) * W + xx) * C + c0);
 #pragma unroll
-          for (int j = 0; j < V; ++j) o[j] = (T)((float)g[j] * gelu_grad_f(acc[t][j]));
+          for (int j = 0; j < V; ++j) o[j] = (T)((float)g[j] * gelu_grad_fast(acc[t][j]));
         } else if (MODE == 3) {
           VT g = *reinterpret_cast<const VT*>(aux + (((size_t)b * H + yy0) * W + xx) * C + c0);
 #pragma unroll
           for (int j = 0; j < V; ++j) o[j] = (T)(acc[t][j] + (float)g[j]);
         } else {
 #pragma unroll
-          for (int j = 0; j < V; ++j) o[j] = (T)(MODE == 1 ? gelu_f(acc[t][j]) : acc[t][j]);
+          for (int j = 0; j < V; ++j) o[j] = (T)(MODE == 1 ? gelu_fast(acc[t][j]) : acc[t][j]);
         }
         *reinterpret_cast<VT*>(orow + (size_t)xx * C) = o;
       }
@@ -204,8 +196,8 @@ __global__ __launch_bounds__(256) void dwconv3_sw_kernel(const T* __restrict__ x
 #pragma unroll
         for (int j = 0; j < V; ++j) {
           float v = acc[j];
-          if (MODE == 1) v = gelu_f(v);
-          else if (MODE == 2) v = (float)g[t][j] * gelu_grad_f(v);
+          if (MODE == 1) v = gelu_fast(v);
+          else if (MODE == 2) v = (float)g[t][j] * gelu_grad_fast(v);
           else if (MODE == 3) v = v + (float)g[t][j];
           o[j] = (T)v;
         }
@@ -231,11 +223,7 @@ int fwd3_sw_launch(const void* x, const float* wt, const float* bias, const void
   return 0;
 }
 
-// 2 channels per lane (one 4-byte bf16x2 / 8-byte float2 load); one wave = 128 channels of one strip.
-template <typename T> struct Pair;
-template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct Pair<bf16_t> { typedef bf16_t type __attribute__((ext_vector_type(2))); };
-template <> struct Pair<f16_t> { typedef f16_t type __attribute__((ext_vector_type(2))); };
+// The weight-gradient kernels: 2 channels per lane (Vec2: one 4-byte bf16x2 / 8-byte float2 load); one wave = 128 channels of one strip.
 
 // ws[gridDim.x][K*K + 1][C] -> out[(K*K + 1) * C] (= { dw_t | db }); fixed summation order, no atomics
 __global__ __launch_bounds__(256) void dwconv_bww_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, int nblocks,
@@ -273,7 +261,7 @@ template <typename T, int K, int TX>
 __global__ __launch_bounds__(K * 64) void dwconv_bwd_weight_kernel(const T* __restrict__ x, const T* __restrict__ du,
                                                                    float* __restrict__ ws, int has_bias,
                                                                    int B, int H, int W, int C, int ysplit) {
-  typedef typename Pair<T>::type PT;
+  typedef typename Vec2<T>::type PT;
   constexpr int P = K / 2;
   const int lane = threadIdx.x & 63, ky = threadIdx.x >> 6;
   const int c0 = blockIdx.y * 128 + lane * 2;
@@ -355,98 +343,21 @@ __global__ __launch_bounds__(K * 64) void dwconv_bwd_weight_kernel(const T* __re
 // The same weight gradient for up to BW_MAX same-shaped layers in ONE launch (deferred weight-gradient phase: a layer's (input,
 // output-gradient) pair stays in HBM until the backward pass is over, then every depthwise layer of one shape is served together).
 // One layer at [8,32,32,512] is 16 MB: 1024 workgroups of 4 rows each, 4x its bytes in partial sums, and a launch that is over
-// before the chip is busy.  27 such layers are 453 MB: here a workgroup (K waves = K filter rows, as above) walks a whole row range
-// of one image x 128 channels with the accumulators in registers (x fastest, so the column halo re-reads hit L1/L2 at once) and
-// writes ONE partial: partial traffic drops from 4x the input to a few per cent, and the launch is a plain HBM stream.
+// before the chip is busy.  27 such layers are 453 MB: here a workgroup walks a whole row range of one image x 128 channels with the
+// accumulators in registers and writes ONE partial: partial traffic drops from 4x the input to a few per cent, and the launch is a
+// plain HBM stream.
 constexpr int BW_MAX = 32;
 struct BwwTable { const void* x[BW_MAX]; const void* du[BW_MAX]; };
 
-template <typename T, int K, int TX>
-__global__ __launch_bounds__(K * 64) void dwconv_bww_batched_kernel(BwwTable tab, float* __restrict__ ws, int has_bias,
-                                                                    int B, int H, int W, int C, int ysplit) {
-  typedef typename Pair<T>::type PT;
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  constexpr int P = K / 2;
-  // The kernel is VALU-bound (56 packed FMAs + 44 conversions per 22 loads), so everything that can be wave-uniform is kept on the
-  // scalar unit: the filter row (readfirstlane), the row base pointers and the boundary tests; the only per-lane address part is
-  // the channel offset, which lets the loads take the scalar-base + VGPR-offset form.
-  const int lane = threadIdx.x & 63, ky = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane2 = lane * 2;
-  const int ypart = blockIdx.x % ysplit, b = (blockIdx.x / ysplit) % B, z = blockIdx.x / (ysplit * B);
-  const size_t img = (size_t)b * H * W * C + (size_t)blockIdx.y * 128;
-  const T* __restrict__ x = (const T*)tab.x[z] + img;
-  const T* __restrict__ du = (const T*)tab.du[z] + img;
-  const int rows_per = (H + ysplit - 1) / ysplit;
-  const int y_begin = ypart * rows_per, y_end = min(H, y_begin + rows_per);
-  f32x2 acc[K], accb = {0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < K; ++t) acc[t] = f32x2{0.f, 0.f};
-  const int ya = max(y_begin, P - ky), yb = min(y_end, H + P - ky);
-  const int XB = (W + TX - 1) / TX;
-  const int nit = max(0, yb - ya) * XB;
-  int fy = ya, fx = 0;                                            // coordinates of the NEXT fetch (x fastest)
-  auto fetch = [&](PT* gr, PT* ir) {
-    const T* grow = du + ((size_t)fy * W + fx) * C;
-    const T* row = x + ((ptrdiff_t)(fy + ky - P) * W + (fx - P)) * (ptrdiff_t)C;
-    if (fx - P >= 0 && fx + TX + P <= W) {                        // straight-line loads
-#pragma unroll
-      for (int t = 0; t < TX; ++t) gr[t] = *reinterpret_cast<const PT*>(grow + t * C + lane2);
-#pragma unroll
-      for (int i = 0; i < TX + K - 1; ++i) ir[i] = *reinterpret_cast<const PT*>(row + i * C + lane2);
-    } else {
-      PT zero; zero[0] = (T)0.f; zero[1] = (T)0.f;
-#pragma unroll
-      for (int t = 0; t < TX; ++t) gr[t] = (fx + t < W) ? *reinterpret_cast<const PT*>(grow + t * C + lane2) : zero;
-#pragma unroll
-      for (int i = 0; i < TX + K - 1; ++i) {
-        const int xx = fx + i - P;
-        ir[i] = (xx >= 0 && xx < W) ? *reinterpret_cast<const PT*>(row + i * C + lane2) : zero;
-      }
-    }
-    fx += TX;
-    if (fx >= W) { fx = 0; ++fy; }
-  };
-  auto compute = [&](const PT* gr, const PT* ir) {
-    f32x2 g[TX], in[TX + K - 1];
-#pragma unroll
-    for (int t = 0; t < TX; ++t) g[t] = f32x2{(float)gr[t][0], (float)gr[t][1]};
-#pragma unroll
-    for (int i = 0; i < TX + K - 1; ++i) in[i] = f32x2{(float)ir[i][0], (float)ir[i][1]};
-    if (ky == P) {
-#pragma unroll
-      for (int t = 0; t < TX; ++t) accb += g[t];
-    }
-#pragma unroll
-    for (int kx = 0; kx < K; ++kx)
-#pragma unroll
-      for (int t = 0; t < TX; ++t) acc[kx] = __builtin_elementwise_fma(g[t], in[t + kx], acc[kx]);
-  };
-  // two register sets, alternating roles: the loads of tile it+1 are in flight while tile it is consumed, without register copies
-  PT gA[TX], iA[TX + K - 1], gB[TX], iB[TX + K - 1];
-  if (nit > 0) fetch(gA, iA);
-  for (int it = 0; it < nit; it += 2) {
-    if (it + 1 < nit) fetch(gB, iB);
-    compute(gA, iA);
-    if (it + 1 >= nit) break;
-    if (it + 2 < nit) fetch(gA, iA);
-    compute(gB, iB);
-  }
-  // ws[z][b * ysplit + ypart][K*K + 1][C]
-  float* wsb = ws + (size_t)blockIdx.x * (K * K + 1) * C + blockIdx.y * 128 + lane2;
-#pragma unroll
-  for (int t = 0; t < K; ++t) *reinterpret_cast<f32x2*>(wsb + (size_t)(ky * K + t) * C) = acc[t];
-  if (ky == P) *reinterpret_cast<f32x2*>(wsb + (size_t)(K * K) * C) = has_bias ? accb : f32x2{0.f, 0.f};
-}
-
-// Sliding-window variant of the batched weight gradient (the default): ONE wave owns all K filter rows of an 8-column strip x 128
-// channels and walks down the image.  Each input row is loaded once per wave (the K-waves-per-workgroup kernel above loads it K times,
-// and its 7x L1/L2 re-read volume, not HBM, bounds it: 1.3 TB/s at 27 x [8,32,32,512]); the K gradient rows it meets (output rows
+// Sliding window: ONE wave owns all K filter rows of an 8-column strip x 128 channels and walks down the image.  Each input row is
+// loaded once per wave (measured: a K-waves-per-workgroup kernel in the style of dwconv_bwd_weight_kernel loads it K times, and its
+// 7x L1/L2 re-read volume, not HBM, bounded it: 1.3 TB/s at 27 x [8,32,32,512]); the K gradient rows it meets (output rows
 // r-P..r+P) sit in a register window that shifts by one row per step.  K*K accumulators x 2 channels per lane; the 4 waves of a
 // workgroup (4 neighbouring strips) add their partials through LDS in a fixed order, so a workgroup writes one partial row set.
 template <typename T, int K, int TX, int NW>
 __global__ __launch_bounds__(NW * 64) void dwconv_bww_sw_kernel(BwwTable tab, float* __restrict__ ws, int has_bias,
                                                                 int B, int H, int W, int C, int ysplit, int xgroups) {
-  typedef typename Pair<T>::type PT;
+  typedef typename Vec2<T>::type PT;
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int P = K / 2, KK = K * K;
   extern __shared__ float red[];                                  // [NW - 1][KK + 1][128]
@@ -624,8 +535,7 @@ int fwd_launch(const void* x, const float* wt, const float* bias, const void* au
 // columns = B * ceil(W/TX) strip columns per channel block; split each column into `ysplit` row ranges until ~1024 workgroups exist
 static int bww_ysplit(int B, int H, int W, int C, int TX, int K) {
   const int64_t cols = (int64_t)B * cdiv(W, TX) * (C / 128);
-  static const int64_t t3 = getenv("DGTD_BWW_TARGET_K3") ? atol(getenv("DGTD_BWW_TARGET_K3")) : 4096;
-  static const int64_t t7 = getenv("DGTD_BWW_TARGET_K7") ? atol(getenv("DGTD_BWW_TARGET_K7")) : 1024;
+  static const int64_t t3 = env_int("DGTD_BWW_TARGET_K3", 4096), t7 = env_int("DGTD_BWW_TARGET_K7", 1024);
   const int64_t target = K == 3 ? t3 : t7;       // workgroups are K waves: keep ~8-12k waves in flight
   int ys = 1;
   while (ys < H && cols * ys < target && (H / (ys * 2)) >= 4) ys *= 2;
@@ -648,20 +558,17 @@ int bww_launch(const void* x, const void* du, float* grads, int has_bias, void* 
   return 0;
 }
 
-// Launch geometry of the batched weight gradient.  Sliding-window kernel (default): a workgroup = 4 neighbouring 8-column strips x a
-// row range x 128 channels; row ranges are halved until ~1024 workgroups exist but never below 16 rows (each range re-reads K-1 halo
-// rows).  DGTD_BWW_SLIDING=0 selects the K-waves-per-workgroup kernel (whole-width row ranges).
-struct BwwGeom { int ys, xg, blocks; bool sliding; };
-static BwwGeom bww_batched_geom(int n, int B, int H, int W, int C, int K) {
-  static const bool sliding = !(getenv("DGTD_BWW_SLIDING") && atoi(getenv("DGTD_BWW_SLIDING")) == 0);
-  static const int64_t target = getenv("DGTD_BWW_BATCHED_WGS") ? atol(getenv("DGTD_BWW_BATCHED_WGS")) : (sliding ? 1024 : 1536);
+// Launch geometry of the batched weight gradient: a workgroup = 4 neighbouring 8-column strips x a row range x 128 channels; row
+// ranges are halved until ~1024 workgroups exist but never below DGTD_BWW_MIN_ROWS rows (each range re-reads K-1 halo rows).
+struct BwwGeom { int ys, xg, blocks; };
+static BwwGeom bww_batched_geom(int n, int B, int H, int W, int C) {
+  static const int64_t target = env_int("DGTD_BWW_BATCHED_WGS", 1024);
+  // measured (n = 27 x [8,32,32,512]): 1728 workgroups of 16 rows beat 864 of 32 although each re-reads K-1 halo rows
+  static const int min_rows = (int)env_int("DGTD_BWW_MIN_ROWS", 8);
   BwwGeom g;
-  g.sliding = sliding;
-  g.xg = sliding ? (int)cdiv(cdiv(W, 8), 4) : 1;
+  g.xg = (int)cdiv(cdiv(W, 8), 4);
   g.ys = 1;
   const int64_t wgs1 = (int64_t)n * B * (C / 128) * g.xg;
-  // measured (n = 27 x [8,32,32,512]): 1728 workgroups of 16 rows beat 864 of 32 although each re-reads K-1 halo rows
-  const int min_rows = sliding ? (int)(getenv("DGTD_BWW_MIN_ROWS") ? atol(getenv("DGTD_BWW_MIN_ROWS")) : 8) : 4;
   while (wgs1 * g.ys < target && H / (g.ys * 2) >= min_rows) g.ys *= 2;
   g.blocks = B * g.ys * g.xg;
   return g;
@@ -677,16 +584,12 @@ int bww_batched_launch(const void* const* x, const void* const* du, int n, int h
     for (int i = 0; i < m; ++i) { tab.x[i] = x[z0 + i]; tab.du[i] = du[z0 + i]; }
     for (int i = m; i < BW_MAX; ++i) { tab.x[i] = nullptr; tab.du[i] = nullptr; }
     float* wsz = ws + (size_t)z0 * g.blocks * (K * K + 1) * C;
-    if (g.sliding) {
-      const size_t lds = (size_t)(NW - 1) * (K * K + 1) * 128 * sizeof(float);
-      static bool once = [] { return hipFuncSetAttribute((const void*)dwconv_bww_sw_kernel<T, K, TX, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         (int)((NW - 1) * (K * K + 1) * 128 * sizeof(float))) == hipSuccess; }();
-      (void)once;
-      hipLaunchKernelGGL((dwconv_bww_sw_kernel<T, K, TX, NW>), dim3(m * g.blocks, C / 128), dim3(NW * 64), lds, s, tab, wsz, has_bias, B, H, W, C, g.ys,
-                         g.xg);
-    } else {
-      hipLaunchKernelGGL((dwconv_bww_batched_kernel<T, K, TX>), dim3(m * g.blocks, C / 128), dim3(K * 64), 0, s, tab, wsz, has_bias, B, H, W, C, g.ys);
-    }
+    const size_t lds = (size_t)(NW - 1) * (K * K + 1) * 128 * sizeof(float);
+    static bool once = [] { return hipFuncSetAttribute((const void*)dwconv_bww_sw_kernel<T, K, TX, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       (int)((NW - 1) * (K * K + 1) * 128 * sizeof(float))) == hipSuccess; }();
+    (void)once;
+    hipLaunchKernelGGL((dwconv_bww_sw_kernel<T, K, TX, NW>), dim3(m * g.blocks, C / 128), dim3(NW * 64), lds, s, tab, wsz, has_bias, B, H, W, C, g.ys,
+                       g.xg);
     DGTD_CHECK_LAUNCH("dwconv_bww_batched");
   }
   return 0;
@@ -696,7 +599,7 @@ int bww_batched_launch(const void* const* x, const void* const* du, int n, int h
 
 extern "C" int dgtd_dwconv_bwd_weight_batched_blocks(int n, int B, int H, int W, int C, int K) {
   (void)K;
-  return C % 128 == 0 && n > 0 ? bww_batched_geom(n, B, H, W, C, K).blocks : 0;
+  return C % 128 == 0 && n > 0 ? bww_batched_geom(n, B, H, W, C).blocks : 0;
 }
 
 extern "C" int dgtd_dwconv_bwd_weight_batched(const void* const* x, const void* const* du, int n, int has_bias, void* workspace, int B, int H,
@@ -709,14 +612,9 @@ extern "C" int dgtd_dwconv_bwd_weight_batched(const void* const* x, const void* 
   for (int i = 0; i < n; ++i) DGTD_REQUIRE(x[i] && du[i], "dwconv_bwd_weight_batched: null tensor in layer %d", i);
   DGTD_PROF(s, DGTD_HBM, 2.0 * dgtd_esize(dt) * n * B * H * W * C, "dgtd_dwconv_bwd_weight_batched[n%d,k%d,%dx%dx%d]", n, K, H, W, C);
   hipStream_t st = (hipStream_t)s;
-  const BwwGeom ys = bww_batched_geom(n, B, H, W, C, K);
+  const BwwGeom ys = bww_batched_geom(n, B, H, W, C);
   float* ws = (float*)workspace;
-  if (dt == DGTD_BF16) return K == 7 ? bww_batched_launch<bf16_t, 7, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st)
-                                     : bww_batched_launch<bf16_t, 3, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st);
-  if (dt == DGTD_F16) return K == 7 ? bww_batched_launch<f16_t, 7, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st)
-                                    : bww_batched_launch<f16_t, 3, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st);
-  return K == 7 ? bww_batched_launch<float, 7, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st)
-                : bww_batched_launch<float, 3, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st);
+  DGTD_DISPATCH(dt, DGTD_DISPATCH_K37(K, return (bww_batched_launch<T_, K_, 8>(x, du, n, has_bias, ws, B, H, W, C, ys, st))));
 }
 
 extern "C" int dgtd_dwconv_fwd(const void* x, const float* w_t, const float* bias, const void* aux, void* y, int B, int H, int W,
@@ -729,27 +627,16 @@ extern "C" int dgtd_dwconv_fwd(const void* x, const float* w_t, const float* bia
   DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "dwconv_fwd: bad dtype %d", (int)dt);
   // measured (profiles/r01_ops_device_times.txt): the LDS-tiled kernel wins 1.6-1.8x for 7x7 (49-tap halo reuse); for 3x3 the direct
   // kernel with 16-byte loads is as fast or faster
-  if (K == 7 && C % 128 == 0 && use_tiled()) return dgtd_dwconv_tiled_fwd(x, w_t, bias, aux, y, B, H, W, C, K, mode, dt, st);
-  static const bool sw3 = !(getenv("DGTD_DWCONV3_SLIDING") && getenv("DGTD_DWCONV3_SLIDING")[0] == '0');
-  if (K == 3 && C % 4 == 0 && sw3 && H >= 8) {
-    if (dt == DGTD_BF16) return fwd3_sw_launch<bf16_t>(x, w_t, bias, aux, y, B, H, W, C, mode, st);
-    if (dt == DGTD_F16) return fwd3_sw_launch<f16_t>(x, w_t, bias, aux, y, B, H, W, C, mode, st);
-    return fwd3_sw_launch<float>(x, w_t, bias, aux, y, B, H, W, C, mode, st);
-  }
-  if (dt == DGTD_BF16) return K == 7 ? fwd_launch<bf16_t, 4, 7, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st)
-                                     : fwd_launch<bf16_t, 8, 3, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st);
-  if (dt == DGTD_F16) return K == 7 ? fwd_launch<f16_t, 4, 7, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st)
-                                    : fwd_launch<f16_t, 8, 3, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st);
-  if (dt == DGTD_F32) return K == 7 ? fwd_launch<float, 4, 7, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st)
-                                    : fwd_launch<float, 4, 3, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st);
-  DGTD_FAIL(2, "dwconv_fwd: bad dtype %d", (int)dt);
+  if (K == 7 && C % 128 == 0) return dgtd_dwconv_tiled_fwd(x, w_t, bias, aux, y, B, H, W, C, K, mode, dt, st);
+  if (K == 3 && C % 4 == 0 && H >= 8) DGTD_DISPATCH(dt, return fwd3_sw_launch<T_>(x, w_t, bias, aux, y, B, H, W, C, mode, st));
+  // direct strip kernel: 4 channels per lane for 7x7, one 16-byte vector (8 x 16-bit / 4 x fp32) for 3x3
+  if (K == 7) DGTD_DISPATCH(dt, return (fwd_launch<T_, 4, 7, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st)));
+  DGTD_DISPATCH(dt, return (fwd_launch<T_, Vec16<T_>::N, 3, 4>(x, w_t, bias, aux, y, B, H, W, C, mode, st)));
 }
 
 extern "C" int64_t dgtd_dwconv_bwd_weight_workspace(int B, int H, int W, int C, int K) {
   const int ys = bww_ysplit(B, H, W, C, 8, K);
-  const int64_t direct = (int64_t)B * cdiv(W, 8) * ys;
-  const int64_t tiled = C % 128 == 0 ? dgtd_dwconv_tiled_bww_groups(B, H, W, C) : 0;
-  return std::max(direct, tiled) * (K * K + 1) * C * sizeof(float);
+  return (int64_t)B * cdiv(W, 8) * ys * (K * K + 1) * C * sizeof(float);
 }
 
 extern "C" int dgtd_dwconv_bwd_weight(const void* x, const void* du, float* grads, int has_bias, void* workspace, int B, int H, int W,
@@ -760,16 +647,9 @@ extern "C" int dgtd_dwconv_bwd_weight(const void* x, const void* du, float* grad
   hipStream_t st = (hipStream_t)s;
   DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "dwconv_bwd_weight: bad dtype %d", (int)dt);
   DGTD_REQUIRE(C % 128 == 0, "dwconv_bwd_weight: C=%d must be a multiple of 128", C);
-  // measured: the K-wave direct kernel below beats the LDS-tiled weight gradient on every shape of the model (its accumulators
-  // never leave the wave); the tiled variant stays selectable for experiments
-  if (use_tiled() && getenv("DGTD_DWCONV_TILED_BWW")) return dgtd_dwconv_tiled_bww(x, du, grads, has_bias, workspace, B, H, W, C, K, dt, st);
-  if (dt == DGTD_BF16) return K == 7 ? bww_launch<bf16_t, 7, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st)
-                                     : bww_launch<bf16_t, 3, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st);
-  if (dt == DGTD_F16) return K == 7 ? bww_launch<f16_t, 7, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st)
-                                    : bww_launch<f16_t, 3, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st);
-  if (dt == DGTD_F32) return K == 7 ? bww_launch<float, 7, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st)
-                                    : bww_launch<float, 3, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st);
-  DGTD_FAIL(2, "dwconv_bwd_weight: bad dtype %d", (int)dt);
+  // measured: the K-wave direct kernel beat an LDS-tiled weight gradient on every shape of the model (its accumulators never leave
+  // the wave)
+  DGTD_DISPATCH(dt, DGTD_DISPATCH_K37(K, return (bww_launch<T_, K_, 8>(x, du, grads, has_bias, workspace, B, H, W, C, st))));
 }
 
 extern "C" int dgtd_dwconv_bwd_weight_partial(const void* x, const void* du, int has_bias, void* workspace, int B, int H, int W, int C, int K,
@@ -780,21 +660,14 @@ extern "C" int dgtd_dwconv_bwd_weight_partial(const void* x, const void* du, int
   DGTD_REQUIRE(C % 128 == 0, "dwconv_bwd_weight_partial: C=%d must be a multiple of 128", C);
   DGTD_PROF(s, DGTD_HBM, 2.0 * dgtd_esize(dt) * B * H * W * C, "dgtd_dwconv_bwd_weight[k%d,%dx%dx%d]", K, H, W, C);
   hipStream_t st = (hipStream_t)s;
-  if (dt == DGTD_BF16) return K == 7 ? bww_launch<bf16_t, 7, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks)
-                                     : bww_launch<bf16_t, 3, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks);
-  if (dt == DGTD_F16) return K == 7 ? bww_launch<f16_t, 7, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks)
-                                    : bww_launch<f16_t, 3, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks);
-  return K == 7 ? bww_launch<float, 7, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks)
-                : bww_launch<float, 3, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks);
+  DGTD_DISPATCH(dt, DGTD_DISPATCH_K37(K, return (bww_launch<T_, K_, 8>(x, du, nullptr, has_bias, workspace, B, H, W, C, st, nblocks))));
 }
 
 extern "C" int dgtd_dwconv_pack(const void* w, const void* bias, float* packed, int C, int K, dgtd_dtype wdt, dgtd_stream s) {
   DGTD_REQUIRE(C > 0 && (K == 3 || K == 7), "dwconv_pack: bad sizes C=%d K=%d", C, K);
   const int KK = K * K, grid = (int)cdiv((int64_t)KK * C, 256);
-  if (wdt == DGTD_BF16) hipLaunchKernelGGL(dwconv_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const bf16_t*)w, (const bf16_t*)bias, packed, C, KK);
-  else if (wdt == DGTD_F16) hipLaunchKernelGGL(dwconv_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const f16_t*)w, (const f16_t*)bias, packed, C, KK);
-  else if (wdt == DGTD_F32) hipLaunchKernelGGL(dwconv_pack_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)w, (const float*)bias, packed, C, KK);
-  else DGTD_FAIL(2, "dwconv_pack: bad dtype %d", (int)wdt);
+  DGTD_REQUIRE(DGTD_IS_HALF(wdt) || wdt == DGTD_F32, "dwconv_pack: bad dtype %d", (int)wdt);
+  DGTD_DISPATCH(wdt, hipLaunchKernelGGL(dwconv_pack_kernel<T_>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const T_*)w, (const T_*)bias, packed, C, KK));
   DGTD_CHECK_LAUNCH("dwconv_pack");
   return 0;
 }
@@ -814,9 +687,7 @@ extern "C" int dgtd_dwconv_pack_batched(const void* const* w, const void* const*
       most = std::max(most, t.KK[i] * t.C[i]);
     }
     const dim3 grid((unsigned)cdiv(most, 256), (unsigned)m);
-    if (wdt == DGTD_BF16) hipLaunchKernelGGL(dwconv_pack_batched_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, t);
-    else if (wdt == DGTD_F16) hipLaunchKernelGGL(dwconv_pack_batched_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)s, t);
-    else hipLaunchKernelGGL(dwconv_pack_batched_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, t);
+    DGTD_DISPATCH(wdt, hipLaunchKernelGGL(dwconv_pack_batched_kernel<T_>, grid, dim3(256), 0, (hipStream_t)s, t));
     DGTD_CHECK_LAUNCH("dwconv_pack_batched");
   }
   return 0;
@@ -825,10 +696,8 @@ extern "C" int dgtd_dwconv_pack_batched(const void* const* w, const void* const*
 extern "C" int dgtd_dwconv_unpack_grads(const float* grads, void* dw, void* db, int C, int K, dgtd_dtype wdt, dgtd_stream s) {
   DGTD_REQUIRE(C > 0 && (K == 3 || K == 7), "dwconv_unpack_grads: bad sizes C=%d K=%d", C, K);
   const int KK = K * K, grid = (int)cdiv((int64_t)KK * C, 256);
-  if (wdt == DGTD_BF16) hipLaunchKernelGGL(dwconv_unpack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, grads, (bf16_t*)dw, (bf16_t*)db, C, KK);
-  else if (wdt == DGTD_F16) hipLaunchKernelGGL(dwconv_unpack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, grads, (f16_t*)dw, (f16_t*)db, C, KK);
-  else if (wdt == DGTD_F32) hipLaunchKernelGGL(dwconv_unpack_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, grads, (float*)dw, (float*)db, C, KK);
-  else DGTD_FAIL(2, "dwconv_unpack_grads: bad dtype %d", (int)wdt);
+  DGTD_REQUIRE(DGTD_IS_HALF(wdt) || wdt == DGTD_F32, "dwconv_unpack_grads: bad dtype %d", (int)wdt);
+  DGTD_DISPATCH(wdt, hipLaunchKernelGGL(dwconv_unpack_kernel<T_>, dim3(grid), dim3(256), 0, (hipStream_t)s, grads, (T_*)dw, (T_*)db, C, KK));
   DGTD_CHECK_LAUNCH("dwconv_unpack_grads");
   return 0;
 }

@@ -109,9 +109,7 @@ struct MrTable {
 };
 
 __device__ __forceinline__ void mr_store(void* out, int dt, int i, float v) {
-  if (dt == DGTD_BF16) ((bf16_t*)out)[i] = (bf16_t)v;
-  else if (dt == DGTD_F16) ((f16_t*)out)[i] = (f16_t)v;
-  else ((float*)out)[i] = v;
+  DGTD_DISPATCH(dt, ((T_*)out)[i] = (T_)v);
 }
 
 __global__ __launch_bounds__(256) void multi_reduce_kernel(MrTable t) {
@@ -317,10 +315,8 @@ extern "C" int dgtd_scale_residual_bias_bwd_partial(const void* g, const void* y
   DGTD_REQUIRE(rows > 0 && C > 0 && rows_per_sample > 0 && nblocks, "scale_residual_bias_bwd_partial: bad sizes");
   DGTD_PROF(st, DGTD_HBM, (gamma ? 3.0 : 2.0) * dgtd_esize(dt) * rows * C, "dgtd_scale_residual_bias_bwd[rows=%lld,C=%d]", (long long)rows, C);
   hipStream_t h = (hipStream_t)st;
-  if (dt == DGTD_F16) return colsum2_launch<f16_t, 3>(g, y, s, gamma, dy, nullptr, nullptr, 0, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd", nblocks);
-  if (dt == DGTD_BF16) return colsum2_launch<bf16_t, 3>(g, y, s, gamma, dy, nullptr, nullptr, 0, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd", nblocks);
-  if (dt == DGTD_F32) return colsum2_launch<float, 3>(g, y, s, gamma, dy, nullptr, nullptr, 0, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd", nblocks);
-  DGTD_FAIL(2, "scale_residual_bias_bwd_partial: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "scale_residual_bias_bwd_partial: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return (colsum2_launch<T_, 3>(g, y, s, gamma, dy, nullptr, nullptr, 0, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd", nblocks)));
 }
 
 extern "C" int dgtd_gelu_bias_bwd_partial(const void* g, const void* pre, void* dpre, void* workspace, int64_t rows, int C, dgtd_dtype dt,
@@ -328,19 +324,15 @@ extern "C" int dgtd_gelu_bias_bwd_partial(const void* g, const void* pre, void* 
   DGTD_REQUIRE(rows > 0 && C > 0 && nblocks, "gelu_bias_bwd_partial: bad sizes");
   DGTD_PROF(st, DGTD_HBM, 3.0 * dgtd_esize(dt) * rows * C, "dgtd_gelu_bias_bwd[rows=%lld,C=%d]", (long long)rows, C);
   hipStream_t h = (hipStream_t)st;
-  if (dt == DGTD_F16) return colsum2_launch<f16_t, 4>(g, pre, nullptr, nullptr, dpre, nullptr, nullptr, 0, workspace, rows, C, 1, h, "gelu_bias_bwd", nblocks);
-  if (dt == DGTD_BF16) return colsum2_launch<bf16_t, 4>(g, pre, nullptr, nullptr, dpre, nullptr, nullptr, 0, workspace, rows, C, 1, h, "gelu_bias_bwd", nblocks);
-  if (dt == DGTD_F32) return colsum2_launch<float, 4>(g, pre, nullptr, nullptr, dpre, nullptr, nullptr, 0, workspace, rows, C, 1, h, "gelu_bias_bwd", nblocks);
-  DGTD_FAIL(2, "gelu_bias_bwd_partial: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "gelu_bias_bwd_partial: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return (colsum2_launch<T_, 4>(g, pre, nullptr, nullptr, dpre, nullptr, nullptr, 0, workspace, rows, C, 1, h, "gelu_bias_bwd", nblocks)));
 }
 
 extern "C" int dgtd_colsum_partial(const void* x, void* workspace, int64_t rows, int C, dgtd_dtype dt, int* nblocks, dgtd_stream st) {
   DGTD_REQUIRE(rows > 0 && C > 0 && nblocks, "colsum_partial: bad sizes");
   DGTD_PROF(st, DGTD_HBM, 1.0 * dgtd_esize(dt) * rows * C, "dgtd_colsum[rows=%lld,C=%d]", (long long)rows, C);
-  if (dt == DGTD_F16) return colsum_launch<f16_t, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, rows, C, 1, (hipStream_t)st, "colsum", 0, nblocks);
-  if (dt == DGTD_BF16) return colsum_launch<bf16_t, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, rows, C, 1, (hipStream_t)st, "colsum", 0, nblocks);
-  if (dt == DGTD_F32) return colsum_launch<float, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, rows, C, 1, (hipStream_t)st, "colsum", 0, nblocks);
-  DGTD_FAIL(2, "colsum_partial: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "colsum_partial: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return (colsum_launch<T_, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, rows, C, 1, (hipStream_t)st, "colsum", 0, nblocks)));
 }
 
 extern "C" int dgtd_scale_residual_fwd(const void* x, const void* y, const float* s, const float* gamma, void* out, int64_t rows,
@@ -350,10 +342,9 @@ extern "C" int dgtd_scale_residual_fwd(const void* x, const void* y, const float
   const int V = DGTD_IS_HALF(dt) ? 8 : 4;
   DGTD_REQUIRE(C % V == 0, "scale_residual_fwd: C=%d must be a multiple of %d", C, V);
   const int grid = (int)std::min<int64_t>(cdiv(rows * (C / V), 256), 256 * 16);
-  if (dt == DGTD_BF16) hipLaunchKernelGGL(scale_residual_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)st, (const bf16_t*)x, (const bf16_t*)y, s, gamma, (bf16_t*)out, rows, C, rows_per_sample);
-  else if (dt == DGTD_F16) hipLaunchKernelGGL(scale_residual_fwd_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)st, (const f16_t*)x, (const f16_t*)y, s, gamma, (f16_t*)out, rows, C, rows_per_sample);
-  else if (dt == DGTD_F32) hipLaunchKernelGGL(scale_residual_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)st, (const float*)x, (const float*)y, s, gamma, (float*)out, rows, C, rows_per_sample);
-  else DGTD_FAIL(2, "scale_residual_fwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "scale_residual_fwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(scale_residual_fwd_kernel<T_>, dim3(grid), dim3(256), 0, (hipStream_t)st, (const T_*)x, (const T_*)y, s, gamma, (T_*)out, rows, C,
+                                       rows_per_sample));
   DGTD_CHECK_LAUNCH("scale_residual_fwd");
   return 0;
 }
@@ -366,13 +357,9 @@ extern "C" int dgtd_scale_residual_bwd(const void* g, const void* y, const float
   DGTD_REQUIRE(rows > 0 && C > 0 && rows_per_sample > 0, "scale_residual_bwd: bad sizes");
   DGTD_REQUIRE((gamma == nullptr) == (dgamma == nullptr), "scale_residual_bwd: gamma and dgamma go together");
   hipStream_t h = (hipStream_t)st;
-  if (dt == DGTD_BF16) return gamma ? colsum_launch<bf16_t, 1>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd")
-                                    : colsum_launch<bf16_t, 2>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd");
-  if (dt == DGTD_F16) return gamma ? colsum_launch<f16_t, 1>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd")
-                                   : colsum_launch<f16_t, 2>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd");
-  if (dt == DGTD_F32) return gamma ? colsum_launch<float, 1>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd")
-                                   : colsum_launch<float, 2>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd");
-  DGTD_FAIL(2, "scale_residual_bwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "scale_residual_bwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return gamma ? (colsum_launch<T_, 1>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd"))
+                                 : (colsum_launch<T_, 2>(g, y, s, gamma, dy, dgamma, workspace, rows, C, rows_per_sample, h, "scale_residual_bwd")));
 }
 
 extern "C" int dgtd_colsum(const void* x, void* out, dgtd_dtype out_dt, void* workspace, int64_t rows, int C, dgtd_dtype dt, dgtd_stream st) {
@@ -380,10 +367,8 @@ extern "C" int dgtd_colsum(const void* x, void* out, dgtd_dtype out_dt, void* wo
   DGTD_REQUIRE(rows > 0 && C > 0, "colsum: bad sizes");
   DGTD_REQUIRE(out_dt == DGTD_F32 || DGTD_IS_HALF(out_dt), "colsum: bad output dtype %d", (int)out_dt);
   const int ob = (int)out_dt;
-  if (dt == DGTD_BF16) return colsum_launch<bf16_t, 0>(x, nullptr, nullptr, nullptr, nullptr, out, workspace, rows, C, 1, (hipStream_t)st, "colsum", ob);
-  if (dt == DGTD_F16) return colsum_launch<f16_t, 0>(x, nullptr, nullptr, nullptr, nullptr, out, workspace, rows, C, 1, (hipStream_t)st, "colsum", ob);
-  if (dt == DGTD_F32) return colsum_launch<float, 0>(x, nullptr, nullptr, nullptr, nullptr, out, workspace, rows, C, 1, (hipStream_t)st, "colsum", ob);
-  DGTD_FAIL(2, "colsum: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "colsum: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return (colsum_launch<T_, 0>(x, nullptr, nullptr, nullptr, nullptr, out, workspace, rows, C, 1, (hipStream_t)st, "colsum", ob)));
 }
 
 extern "C" int64_t dgtd_colsum2_workspace(int C) { return (int64_t)EW_MAX_BLOCKS * 2 * C * sizeof(float); }
@@ -397,10 +382,8 @@ extern "C" int dgtd_scale_residual_bias_bwd(const void* g, const void* y, const 
   DGTD_REQUIRE(bias_dt == DGTD_F32 || DGTD_IS_HALF(bias_dt), "scale_residual_bias_bwd: bad bias dtype %d", (int)bias_dt);
   hipStream_t h = (hipStream_t)st;
   const int ob = (int)bias_dt;
-  if (dt == DGTD_F16) return colsum2_launch<f16_t, 3>(g, y, s, gamma, dy, dgamma, dbias, ob, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd");
-  if (dt == DGTD_BF16) return colsum2_launch<bf16_t, 3>(g, y, s, gamma, dy, dgamma, dbias, ob, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd");
-  if (dt == DGTD_F32) return colsum2_launch<float, 3>(g, y, s, gamma, dy, dgamma, dbias, ob, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd");
-  DGTD_FAIL(2, "scale_residual_bias_bwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "scale_residual_bias_bwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return (colsum2_launch<T_, 3>(g, y, s, gamma, dy, dgamma, dbias, ob, workspace, rows, C, rows_per_sample, h, "scale_residual_bias_bwd")));
 }
 
 extern "C" int dgtd_gelu_bias_bwd(const void* g, const void* pre, void* dpre, void* dbias, dgtd_dtype bias_dt, void* workspace,
@@ -410,8 +393,6 @@ extern "C" int dgtd_gelu_bias_bwd(const void* g, const void* pre, void* dpre, vo
   DGTD_REQUIRE(bias_dt == DGTD_F32 || DGTD_IS_HALF(bias_dt), "gelu_bias_bwd: bad bias dtype %d", (int)bias_dt);
   hipStream_t h = (hipStream_t)st;
   const int ob = (int)bias_dt;
-  if (dt == DGTD_F16) return colsum2_launch<f16_t, 4>(g, pre, nullptr, nullptr, dpre, nullptr, dbias, ob, workspace, rows, C, 1, h, "gelu_bias_bwd");
-  if (dt == DGTD_BF16) return colsum2_launch<bf16_t, 4>(g, pre, nullptr, nullptr, dpre, nullptr, dbias, ob, workspace, rows, C, 1, h, "gelu_bias_bwd");
-  if (dt == DGTD_F32) return colsum2_launch<float, 4>(g, pre, nullptr, nullptr, dpre, nullptr, dbias, ob, workspace, rows, C, 1, h, "gelu_bias_bwd");
-  DGTD_FAIL(2, "gelu_bias_bwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "gelu_bias_bwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return (colsum2_launch<T_, 4>(g, pre, nullptr, nullptr, dpre, nullptr, dbias, ob, workspace, rows, C, 1, h, "gelu_bias_bwd")));
 }

@@ -23,7 +23,6 @@
 // reads back), so those outputs are rounded twice.  blockIdx -> tile mapping is XCD-aware (the column tiles of one row
 // panel of A run on one XCD's L2).  MFMA-bound above K ~ 512, HBM-bound below: 2·M·N·K flop over (M·K + N·K + n_out·M·N + ...)·e bytes.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -335,10 +334,9 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(TrTable t) {
 }
 
 // A/B knobs (read once): DGTD_GEMM_STAGES = 2 | 3 (pipeline form), DGTD_GEMM_WIDE_MIN = fewest 128-wide tiles for which the wide tile is taken
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 template <typename T, int EPI>
 int launch(const GemmArgs& a0, hipStream_t st) {
-  static const int force_stages = env_int("DGTD_GEMM_STAGES", 0), wide_min = env_int("DGTD_GEMM_WIDE_MIN", 192), dbg = env_int("DGTD_GEMM_DBG", 0);
+  static const int force_stages = (int)env_int("DGTD_GEMM_STAGES", 0), wide_min = (int)env_int("DGTD_GEMM_WIDE_MIN", 192), dbg = (int)env_int("DGTD_GEMM_DBG", 0);
   GemmArgs a = a0;
   a.dbg = dbg;
   const int tiles_m = a.M / BM;
@@ -360,8 +358,7 @@ int launch(const GemmArgs& a0, hipStream_t st) {
 
 template <int EPI>
 int dispatch(const GemmArgs& a, dgtd_dtype dt, hipStream_t st) {
-  if (dt == DGTD_F16) return launch<f16_t, EPI>(a, st);
-  return launch<bf16_t, EPI>(a, st);
+  DGTD_DISPATCH_HALF(dt, return (launch<T_, EPI>(a, st)));
 }
 
 int check_common(const void* a, const void* b, const void* d, int M, int N, int K, dgtd_dtype dt, const char* name) {

@@ -301,6 +301,5 @@ extern "C" int dgtd_gemm_wgrad_batched(const void* dy, const void* x, void* dw, 
   const int S = (int)cdiv(M / TS, per);
   DGTD_REQUIRE(S == 1 || (workspace && (uintptr_t)workspace % 16 == 0), "gemm_wgrad: %d token chunks need a 16-byte aligned workspace", S);
   WgradArgs a{dy, x, dw, (float*)workspace, M, N, K, K / tile_n(K), S, per, s_dy, s_x, s_dw};
-  if (dt == DGTD_F16) return launch<f16_t>(a, batch, (hipStream_t)s);
-  return launch<bf16_t>(a, batch, (hipStream_t)s);
+  DGTD_DISPATCH_HALF(dt, return launch<T_>(a, batch, (hipStream_t)s));
 }

@@ -87,58 +87,11 @@ __global__ __launch_bounds__(256) void pooled_sum_kernel(const T* __restrict__ a
   }
 }
 
-// gate[b][c] = sigmoid(W2 relu(W1 (pooled[b]/HW)));  hidden[b][j] kept for the backward.  One workgroup per sample.
-__global__ __launch_bounds__(128) void ca_gate_mlp_kernel(const float* __restrict__ partial, int nparts, float* __restrict__ pooled,
-                                                          const float* __restrict__ w1, const float* __restrict__ w2,
-                                                          float* __restrict__ gate, float* __restrict__ hidden, int HW, int C, int R) {
-  __shared__ float m[128], hdn[32];
-  const int b = blockIdx.x, B = gridDim.x, tid = threadIdx.x;
-  if (tid < C) {
-    float s0 = 0.f, s1 = 0.f;
-    int x = 0;
-    for (; x + 1 < nparts; x += 2) { s0 += partial[((size_t)x * B + b) * C + tid]; s1 += partial[((size_t)(x + 1) * B + b) * C + tid]; }
-    if (x < nparts) s0 += partial[((size_t)x * B + b) * C + tid];
-    const float s = s0 + s1;
-    pooled[b * C + tid] = s;
-    m[tid] = s / (float)HW;
-  }
-  __syncthreads();
-  if (tid < R) {
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += w1[tid * C + c] * m[c];
-    s = fmaxf(s, 0.f);
-    hdn[tid] = s;
-    hidden[b * R + tid] = s;
-  }
-  __syncthreads();
-  if (tid < C) {
-    float s = 0.f;
-    for (int j = 0; j < R; ++j) s += w2[tid * R + j] * hdn[j];
-    gate[b * C + tid] = 1.f / (1.f + expf(-s));
-  }
-}
-
-// out = res * gate[b][c] + x
-template <typename T>
-__global__ __launch_bounds__(256) void ca_apply_kernel(const T* __restrict__ res, const T* __restrict__ x, const float* __restrict__ gate,
-                                                       T* __restrict__ out, int64_t rows, int HW, int C) {
-  typedef typename Vec16<T>::type VT;
-  constexpr int V = Vec16<T>::N;
-  const int CV = C / V;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * CV; i += (int64_t)gridDim.x * 256) {
-    const int cv = (int)(i % CV);
-    const int b = (int)((i / CV) / HW);
-    VT r = *reinterpret_cast<const VT*>(res + i * V), xv = *reinterpret_cast<const VT*>(x + i * V), o;
-#pragma unroll
-    for (int j = 0; j < V; ++j) o[j] = (T)((float)r[j] * gate[b * C + cv * V + j] + (float)xv[j]);
-    *reinterpret_cast<VT*>(out + i * V) = o;
-  }
-}
-
-// The per-sample MLP folded into the apply pass: grid (slices, B); every workgroup recomputes gate[b][:] from the pooled partial sums
-// (C + R*C + C*R MACs, the same arithmetic in the same order as ca_gate_mlp_kernel, so all workgroups of a sample agree bit for bit)
-// and applies it to its slice of the sample; workgroup 0 of the sample also writes pooled / hidden / gate for the backward.  The
-// stand-alone MLP launch was 8.6 us of pure latency (one small workgroup per sample, three dependent phases) in front of a 5 us pass.
+// out = res * gate[b][c] + x with gate[b][c] = sigmoid(W2 relu(W1 (pooled[b]/HW))), the per-sample MLP folded into the apply pass:
+// grid (slices, B); every workgroup recomputes gate[b][:] from the pooled partial sums (C + R*C + C*R MACs in one fixed order, so all
+// workgroups of a sample agree bit for bit) and applies it to its slice of the sample; workgroup 0 of the sample also writes pooled /
+// hidden / gate for the backward.  A stand-alone MLP launch was 8.6 us of pure latency (one small workgroup per sample, three
+// dependent phases) in front of a 5 us pass.
 template <typename T>
 __global__ __launch_bounds__(256) void ca_apply_fused_kernel(const T* __restrict__ res, const T* __restrict__ x, const float* __restrict__ partial,
                                                              int nparts, const float* __restrict__ w1, const float* __restrict__ w2,
@@ -459,10 +412,8 @@ extern "C" int dgtd_prelu_fwd(const void* x, const float* a, void* y, int64_t n,
   DGTD_PROF(s, DGTD_HBM, 2.0 * dgtd_esize(dt) * n, "dgtd_prelu_fwd[n=%lld]", (long long)n);
   const int V = DGTD_IS_HALF(dt) ? 8 : 4;
   DGTD_REQUIRE(n > 0 && n % V == 0, "prelu_fwd: n=%lld must be a positive multiple of %d", (long long)n, V);
-  if (dt == DGTD_F16) hipLaunchKernelGGL(prelu_fwd_kernel<f16_t>, dim3(ew_grid(n / V)), dim3(256), 0, (hipStream_t)s, (const f16_t*)x, a, (f16_t*)y, n);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(prelu_fwd_kernel<bf16_t>, dim3(ew_grid(n / V)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, a, (bf16_t*)y, n);
-  else if (dt == DGTD_F32) hipLaunchKernelGGL(prelu_fwd_kernel<float>, dim3(ew_grid(n / V)), dim3(256), 0, (hipStream_t)s, (const float*)x, a, (float*)y, n);
-  else DGTD_FAIL(2, "prelu_fwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "prelu_fwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(prelu_fwd_kernel<T_>, dim3(ew_grid(n / V)), dim3(256), 0, (hipStream_t)s, (const T_*)x, a, (T_*)y, n));
   DGTD_CHECK_LAUNCH("prelu_fwd");
   return 0;
 }
@@ -472,10 +423,8 @@ extern "C" int dgtd_prelu_bwd(const void* x, const void* g, const float* a, void
   const int V = DGTD_IS_HALF(dt) ? 8 : 4;
   DGTD_REQUIRE(n > 0 && n % V == 0, "prelu_bwd: n=%lld must be a positive multiple of %d", (long long)n, V);
   const int grid = std::min(ew_grid(n / V), 512);
-  if (dt == DGTD_F16) hipLaunchKernelGGL(prelu_bwd_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const f16_t*)x, (const f16_t*)g, a, (f16_t*)dx, da, n);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(prelu_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (const bf16_t*)g, a, (bf16_t*)dx, da, n);
-  else if (dt == DGTD_F32) hipLaunchKernelGGL(prelu_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)x, (const float*)g, a, (float*)dx, da, n);
-  else DGTD_FAIL(2, "prelu_bwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "prelu_bwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(prelu_bwd_kernel<T_>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const T_*)x, (const T_*)g, a, (T_*)dx, da, n));
   DGTD_CHECK_LAUNCH("prelu_bwd");
   return 0;
 }
@@ -487,29 +436,16 @@ extern "C" int dgtd_ca_gate_fwd(const void* res, const void* x, const float* w1,
   const int V = DGTD_IS_HALF(dt) ? 8 : 4;
   DGTD_REQUIRE(B > 0 && HW > 0 && C > 0 && C <= 128 && R > 0 && R <= 32 && C % V == 0, "ca_gate_fwd: unsupported sizes C=%d R=%d", C, R);
   DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "ca_gate_fwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(B <= 65535, "ca_gate_fwd: B=%d", B);
   hipStream_t st = (hipStream_t)s;
   float *pooled = stats, *gate = stats + (size_t)B * C, *hidden = gate + (size_t)B * C, *partial = hidden + (size_t)B * R;
   const int cpr = std::max(1, 256 / C), gx = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(HW, cpr * 8), 64));   // <= 64 slices (the stats / scratch layout), summed per column by the per-sample MLP kernels
-  if (dt == DGTD_F16) hipLaunchKernelGGL((pooled_sum_kernel<f16_t, false>), dim3(gx, B), dim3(256), 0, st, (const f16_t*)res, (const f16_t*)nullptr, partial, HW, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL((pooled_sum_kernel<bf16_t, false>), dim3(gx, B), dim3(256), 0, st, (const bf16_t*)res, (const bf16_t*)nullptr, partial, HW, C);
-  else hipLaunchKernelGGL((pooled_sum_kernel<float, false>), dim3(gx, B), dim3(256), 0, st, (const float*)res, (const float*)nullptr, partial, HW, C);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL((pooled_sum_kernel<T_, false>), dim3(gx, B), dim3(256), 0, st, (const T_*)res, (const T_*)nullptr, partial, HW, C));
   DGTD_CHECK_LAUNCH("ca_pooled_sum");
-  static const bool fused = !(getenv("DGTD_CA_FUSED") && getenv("DGTD_CA_FUSED")[0] == '0');
-  if (fused && B <= 65535) {
-    const int ax = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((int64_t)HW * (C / V), 256 * 2), 128));
-    if (dt == DGTD_F16) hipLaunchKernelGGL(ca_apply_fused_kernel<f16_t>, dim3(ax, B), dim3(256), 0, st, (const f16_t*)res, (const f16_t*)x, (const float*)partial, gx, w1, w2, pooled, hidden, gate, (f16_t*)out, HW, C, R);
-    else if (dt == DGTD_BF16) hipLaunchKernelGGL(ca_apply_fused_kernel<bf16_t>, dim3(ax, B), dim3(256), 0, st, (const bf16_t*)res, (const bf16_t*)x, (const float*)partial, gx, w1, w2, pooled, hidden, gate, (bf16_t*)out, HW, C, R);
-    else hipLaunchKernelGGL(ca_apply_fused_kernel<float>, dim3(ax, B), dim3(256), 0, st, (const float*)res, (const float*)x, (const float*)partial, gx, w1, w2, pooled, hidden, gate, (float*)out, HW, C, R);
-    DGTD_CHECK_LAUNCH("ca_apply_fused");
-    return 0;
-  }
-  hipLaunchKernelGGL(ca_gate_mlp_kernel, dim3(B), dim3(128), 0, st, (const float*)partial, gx, pooled, w1, w2, gate, hidden, HW, C, R);
-  DGTD_CHECK_LAUNCH("ca_gate_mlp");
-  const int64_t rows = (int64_t)B * HW;
-  if (dt == DGTD_F16) hipLaunchKernelGGL(ca_apply_kernel<f16_t>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const f16_t*)res, (const f16_t*)x, (const float*)gate, (f16_t*)out, rows, HW, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(ca_apply_kernel<bf16_t>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const bf16_t*)res, (const bf16_t*)x, (const float*)gate, (bf16_t*)out, rows, HW, C);
-  else hipLaunchKernelGGL(ca_apply_kernel<float>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const float*)res, (const float*)x, (const float*)gate, (float*)out, rows, HW, C);
-  DGTD_CHECK_LAUNCH("ca_apply");
+  const int ax = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((int64_t)HW * (C / V), 256 * 2), 128));
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(ca_apply_fused_kernel<T_>, dim3(ax, B), dim3(256), 0, st, (const T_*)res, (const T_*)x, (const float*)partial, gx, w1, w2,
+                                       pooled, hidden, gate, (T_*)out, HW, C, R));
+  DGTD_CHECK_LAUNCH("ca_apply_fused");
   return 0;
 }
 
@@ -524,26 +460,21 @@ static int ca_gate_bwd_impl(const void* g, const void* res, const float* w1, con
   const float *pooled = stats, *gate = stats + (size_t)B * C, *hidden = gate + (size_t)B * C;
   float *dmean = scratch, *partial = scratch + (size_t)B * C, *dwp = partial + (size_t)64 * B * C;
   const int cpr = std::max(1, 256 / C), gx = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(HW, cpr * 8), 64));   // <= 64 slices (the stats / scratch layout), summed per column by the per-sample MLP kernels
-  if (dt == DGTD_F16) hipLaunchKernelGGL((pooled_sum_kernel<f16_t, true>), dim3(gx, B), dim3(256), 0, st, (const f16_t*)g, (const f16_t*)res, partial, HW, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL((pooled_sum_kernel<bf16_t, true>), dim3(gx, B), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)res, partial, HW, C);
-  else hipLaunchKernelGGL((pooled_sum_kernel<float, true>), dim3(gx, B), dim3(256), 0, st, (const float*)g, (const float*)res, partial, HW, C);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL((pooled_sum_kernel<T_, true>), dim3(gx, B), dim3(256), 0, st, (const T_*)g, (const T_*)res, partial, HW, C));
   DGTD_CHECK_LAUNCH("ca_dgate_sum");
-  static const bool fused = !(getenv("DGTD_CA_FUSED") && getenv("DGTD_CA_FUSED")[0] == '0');
-  if (per_sample || (fused && B <= CA_MAXB)) {
+  if (per_sample || B <= CA_MAXB) {
     const int ax = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((int64_t)HW * (C / V), 256 * 2), 128));
     const size_t lds = (size_t)(416 + (per_sample ? 0 : B * 160)) * sizeof(float);
-    if (dt == DGTD_F16) hipLaunchKernelGGL(ca_apply_bwd_fused_kernel<f16_t>, dim3(ax, B), dim3(256), lds, st, (const f16_t*)g, (const float*)partial, gx, gate, hidden, pooled, w1, w2, (f16_t*)dres, dw1, dw2, HW, C, R, per_sample);
-    else if (dt == DGTD_BF16) hipLaunchKernelGGL(ca_apply_bwd_fused_kernel<bf16_t>, dim3(ax, B), dim3(256), lds, st, (const bf16_t*)g, (const float*)partial, gx, gate, hidden, pooled, w1, w2, (bf16_t*)dres, dw1, dw2, HW, C, R, per_sample);
-    else hipLaunchKernelGGL(ca_apply_bwd_fused_kernel<float>, dim3(ax, B), dim3(256), lds, st, (const float*)g, (const float*)partial, gx, gate, hidden, pooled, w1, w2, (float*)dres, dw1, dw2, HW, C, R, per_sample);
+    DGTD_DISPATCH(dt, hipLaunchKernelGGL(ca_apply_bwd_fused_kernel<T_>, dim3(ax, B), dim3(256), lds, st, (const T_*)g, (const float*)partial, gx, gate, hidden,
+                                         pooled, w1, w2, (T_*)dres, dw1, dw2, HW, C, R, per_sample));
     DGTD_CHECK_LAUNCH("ca_apply_bwd_fused");
     return 0;
   }
   hipLaunchKernelGGL(ca_gate_mlp_bwd_kernel, dim3(B), dim3(128), 0, st, (const float*)partial, gx, gate, hidden, pooled, w1, w2, dmean, dwp, HW, C, R);
   DGTD_CHECK_LAUNCH("ca_gate_mlp_bwd");
   const int64_t rows = (int64_t)B * HW;
-  if (dt == DGTD_F16) hipLaunchKernelGGL(ca_apply_bwd_kernel<f16_t>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const f16_t*)g, gate, (const float*)dmean, (f16_t*)dres, rows, HW, C, (const float*)dwp, dw1, dw2, B, R);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(ca_apply_bwd_kernel<bf16_t>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const bf16_t*)g, gate, (const float*)dmean, (bf16_t*)dres, rows, HW, C, (const float*)dwp, dw1, dw2, B, R);
-  else hipLaunchKernelGGL(ca_apply_bwd_kernel<float>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const float*)g, gate, (const float*)dmean, (float*)dres, rows, HW, C, (const float*)dwp, dw1, dw2, B, R);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(ca_apply_bwd_kernel<T_>, dim3(ew_grid(rows * (C / V))), dim3(256), 0, st, (const T_*)g, gate, (const float*)dmean, (T_*)dres,
+                                       rows, HW, C, (const float*)dwp, dw1, dw2, B, R));
   DGTD_CHECK_LAUNCH("ca_apply_bwd");
   return 0;
 }
@@ -568,10 +499,8 @@ extern "C" int dgtd_bilinear_fwd(const void* x, void* y, int B, int Hi, int Wi, 
   DGTD_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && C % V == 0, "bilinear_fwd: bad sizes (C=%d must be a multiple of %d)", C, V);
   const Axis ah = make_axis(Hi, Ho, align_corners), aw = make_axis(Wi, Wo, align_corners);
   const int grid = ew_grid((int64_t)B * Ho * Wo * (C / V));
-  if (dt == DGTD_F16) hipLaunchKernelGGL(bilinear_fwd_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const f16_t*)x, (f16_t*)y, B, Hi, Wi, Ho, Wo, C, ah, aw);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(bilinear_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)y, B, Hi, Wi, Ho, Wo, C, ah, aw);
-  else if (dt == DGTD_F32) hipLaunchKernelGGL(bilinear_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)x, (float*)y, B, Hi, Wi, Ho, Wo, C, ah, aw);
-  else DGTD_FAIL(2, "bilinear_fwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "bilinear_fwd: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(bilinear_fwd_kernel<T_>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const T_*)x, (T_*)y, B, Hi, Wi, Ho, Wo, C, ah, aw));
   DGTD_CHECK_LAUNCH("bilinear_fwd");
   return 0;
 }
@@ -588,13 +517,10 @@ extern "C" int dgtd_bilinear_bwd(const void* dy, void* dx, int B, int Hi, int Wi
   const float up = ah.scale > 0.f ? 1.f / ah.scale : (float)Ho;
   const int lpi = up >= 6.f ? 16 : (up >= 3.f ? 8 : (up >= 1.5f ? 2 : 1));
   const int grid = ew_grid((int64_t)B * Hi * Wi * (C / V) * lpi);
-#define DGTD_BIL_BWD(T_, L_) hipLaunchKernelGGL((bilinear_bwd_kernel<T_, L_>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T_*)dy, (T_*)dx, B, Hi, Wi, Ho, Wo, C, ah, aw, inv_h, inv_w)
-#define DGTD_BIL_BWD_L(T_) do { if (lpi == 16) DGTD_BIL_BWD(T_, 16); else if (lpi == 8) DGTD_BIL_BWD(T_, 8); else if (lpi == 2) DGTD_BIL_BWD(T_, 2); else DGTD_BIL_BWD(T_, 1); } while (0)
-  if (dt == DGTD_F16) DGTD_BIL_BWD_L(f16_t);
-  else if (dt == DGTD_BF16) DGTD_BIL_BWD_L(bf16_t);
-  else if (dt == DGTD_F32) DGTD_BIL_BWD_L(float);
-  else DGTD_FAIL(2, "bilinear_bwd: bad dtype %d", (int)dt);
-#undef DGTD_BIL_BWD_L
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "bilinear_bwd: bad dtype %d", (int)dt);
+#define DGTD_BIL_BWD(L_) DGTD_DISPATCH(dt, hipLaunchKernelGGL((bilinear_bwd_kernel<T_, L_>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T_*)dy, (T_*)dx, B, Hi, Wi, \
+                                                              Ho, Wo, C, ah, aw, inv_h, inv_w))
+  if (lpi == 16) DGTD_BIL_BWD(16); else if (lpi == 8) DGTD_BIL_BWD(8); else if (lpi == 2) DGTD_BIL_BWD(2); else DGTD_BIL_BWD(1);
 #undef DGTD_BIL_BWD
   DGTD_CHECK_LAUNCH("bilinear_bwd");
   return 0;

@@ -114,10 +114,8 @@ int im2col_launch(const void* x, void* col, const Geo& g, hipStream_t st) {
 
 template <typename TI>
 int im2col_out(const void* x, void* col, const Geo& g, dgtd_dtype col_dt, hipStream_t st) {
-  if (col_dt == DGTD_F32) return im2col_launch<TI, float>(x, col, g, st);
-  if (col_dt == DGTD_BF16) return im2col_launch<TI, bf16_t>(x, col, g, st);
-  if (col_dt == DGTD_F16) return im2col_launch<TI, f16_t>(x, col, g, st);
-  DGTD_FAIL(2, "im2col: bad column dtype %d", (int)col_dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(col_dt) || col_dt == DGTD_F32, "im2col: bad column dtype %d", (int)col_dt);
+  DGTD_DISPATCH(col_dt, return (im2col_launch<TI, T_>(x, col, g, st)));
 }
 
 template <typename T>
@@ -143,10 +141,8 @@ extern "C" int dgtd_im2col(const void* x, void* col, int B, int H, int W, int C,
             "dgtd_im2col[%dx%dx%d,k%d,s%d->%dx%d]", H, W, C, K, stride, Ho, Wo);
   const Geo g{B, H, W, C, K, stride, pad, Ho, Wo, (long)sb, (long)sy, (long)sx, (long)sc};
   hipStream_t st = (hipStream_t)s;
-  if (x_dt == DGTD_F32) return im2col_out<float>(x, col, g, col_dt, st);
-  if (x_dt == DGTD_BF16) return im2col_out<bf16_t>(x, col, g, col_dt, st);
-  if (x_dt == DGTD_F16) return im2col_out<f16_t>(x, col, g, col_dt, st);
-  DGTD_FAIL(2, "im2col: bad input dtype %d", (int)x_dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(x_dt) || x_dt == DGTD_F32, "im2col: bad input dtype %d", (int)x_dt);
+  DGTD_DISPATCH(x_dt, return im2col_out<T_>(x, col, g, col_dt, st));
 }
 
 extern "C" int dgtd_col2im(const void* dcol, void* dx, int B, int H, int W, int C, int K, int stride, int pad, int Ho, int Wo, dgtd_dtype dt,
@@ -156,8 +152,6 @@ extern "C" int dgtd_col2im(const void* dcol, void* dx, int B, int H, int W, int 
             stride, Ho, Wo);
   const Geo g{B, H, W, C, K, stride, pad, Ho, Wo, 0, 0, 0, 1};
   hipStream_t st = (hipStream_t)s;
-  if (dt == DGTD_F32) return col2im_launch<float>(dcol, dx, g, st);
-  if (dt == DGTD_BF16) return col2im_launch<bf16_t>(dcol, dx, g, st);
-  if (dt == DGTD_F16) return col2im_launch<f16_t>(dcol, dx, g, st);
-  DGTD_FAIL(2, "col2im: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(dt) || dt == DGTD_F32, "col2im: bad dtype %d", (int)dt);
+  DGTD_DISPATCH(dt, return col2im_launch<T_>(dcol, dx, g, st));
 }

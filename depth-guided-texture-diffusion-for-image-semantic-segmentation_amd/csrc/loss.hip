@@ -10,7 +10,6 @@
 //   fwd   : per (map k, sample b): A = sum w*bce, I = sum w*sig*gt, U = sum w*(sig+gt); per b: W = sum w   (wave shuffles + atomics)
 //   bwd   : gather per low-res pixel over the <= 16x16 label pixels it touches (transpose of the bilinear sampling)
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -333,7 +332,7 @@ extern "C" int dgtd_ssim_value(const float* x_hp, const float* image, float* out
   DGTD_CHECK_LAUNCH("ssim_minmax");
   // one fp64 atomic per workgroup on ONE address: 6144 of them (256 slices x 24 planes) serialised into most of the kernel's 82 us;
   // 96 slices per plane (2304 atomics) measured best: 105 -> 66 us for the whole value (tools/ssim_time.py)
-  static const int slices = getenv("DGTD_SSIM_SLICES") ? atoi(getenv("DGTD_SSIM_SLICES")) : 96;
+  static const int slices = (int)env_int("DGTD_SSIM_SLICES", 96);
   hipLaunchKernelGGL(ssim_map_kernel, dim3((int)std::max<long>(1, std::min<long>(cdiv((long)S * S, 256), slices)), B * C), dim3(256), 0, st, x_hp, image, (const unsigned*)mm, acc, S);
   DGTD_CHECK_LAUNCH("ssim_map");
   hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(1), 0, st, (const double*)acc, out, 1.0 / (double)n);
@@ -372,8 +371,7 @@ extern "C" int dgtd_seg_loss_bwd(const float* lo, const float* label, const floa
   const float* weit = (const float*)workspace;
   const float* sums = weit + (size_t)B * S * S;
   const float* wsum = sums + (size_t)NMAP * B * 3;
-  static const bool tiled = !(getenv("DGTD_LOSS_BWD_TILED") && getenv("DGTD_LOSS_BWD_TILED")[0] == '0');
-  if (tiled && S == 8 * hs && B <= 65535) {          // the model's x8 up-sampling: every pixel's derivative evaluated once per tile
+  if (S == 8 * hs && B <= 65535) {          // the model's x8 up-sampling: every pixel's derivative evaluated once per tile
     const int tiles = (hs + LT - 1) / LT;
     hipLaunchKernelGGL(loss_bwd_tiled_kernel, dim3(tiles, tiles, B), dim3(256), 0, (hipStream_t)s, lo, label, weit, sums, wsum, mix, gout, dlo, B, S, hs);
   } else {

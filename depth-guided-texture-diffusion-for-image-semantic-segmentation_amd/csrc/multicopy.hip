@@ -88,10 +88,8 @@ int launch_tables(const void* const* tensors, const int64_t* offs, const int64_t
 
 template <typename S>
 int by_dst(const void* const* tensors, const int64_t* offs, const int64_t* ns, int count, void* flat, dgtd_dtype ft, int to_tensors, hipStream_t st) {
-  if (ft == DGTD_F32) return launch_tables<S, float>(tensors, offs, ns, count, flat, to_tensors, st);
-  if (ft == DGTD_BF16) return launch_tables<S, bf16_t>(tensors, offs, ns, count, flat, to_tensors, st);
-  if (ft == DGTD_F16) return launch_tables<S, f16_t>(tensors, offs, ns, count, flat, to_tensors, st);
-  DGTD_FAIL(2, "multi_copy: bad flat dtype %d", (int)ft);
+  DGTD_REQUIRE(DGTD_IS_HALF(ft) || ft == DGTD_F32, "multi_copy: bad flat dtype %d", (int)ft);
+  DGTD_DISPATCH(ft, return (launch_tables<S, T_>(tensors, offs, ns, count, flat, to_tensors, st)));
 }
 
 }  // namespace
@@ -107,8 +105,6 @@ extern "C" int dgtd_multi_copy(const void* const* tensors, const int64_t* offset
   }
   DGTD_PROF(s, DGTD_HBM, total * (dgtd_esize(tensor_dt) + dgtd_esize(flat_dt)), "dgtd_multi_copy[n=%d,elems=%.0f]", n_tensors, total);
   hipStream_t st = (hipStream_t)s;
-  if (tensor_dt == DGTD_F32) return by_dst<float>(tensors, offsets, counts, n_tensors, flat, flat_dt, to_tensors, st);
-  if (tensor_dt == DGTD_BF16) return by_dst<bf16_t>(tensors, offsets, counts, n_tensors, flat, flat_dt, to_tensors, st);
-  if (tensor_dt == DGTD_F16) return by_dst<f16_t>(tensors, offsets, counts, n_tensors, flat, flat_dt, to_tensors, st);
-  DGTD_FAIL(2, "multi_copy: bad tensor dtype %d", (int)tensor_dt);
+  DGTD_REQUIRE(DGTD_IS_HALF(tensor_dt) || tensor_dt == DGTD_F32, "multi_copy: bad tensor dtype %d", (int)tensor_dt);
+  DGTD_DISPATCH(tensor_dt, return by_dst<T_>(tensors, offsets, counts, n_tensors, flat, flat_dt, to_tensors, st));
 }

@@ -132,9 +132,8 @@ extern "C" int dgtd_preprocess(const void* img_u8, void* out, const float* mean_
                      (const int*)bounds_h, (const int*)kk_h, Hin, Win, C, S, kh, flip);
   DGTD_CHECK_LAUNCH("preprocess_horizontal");
   const int gv = (int)std::min<int64_t>(cdiv((int64_t)S * S, 256), 4096);
-  if (out_dt == DGTD_F32) hipLaunchKernelGGL(resize_v_norm_kernel<float>, dim3(gv), dim3(256), 0, st, (const uint8_t*)mid, (float*)out, (const int*)bounds_v, (const int*)kk_v, Hin, C, S, kv, na);
-  else if (out_dt == DGTD_F16) hipLaunchKernelGGL(resize_v_norm_kernel<f16_t>, dim3(gv), dim3(256), 0, st, (const uint8_t*)mid, (f16_t*)out, (const int*)bounds_v, (const int*)kk_v, Hin, C, S, kv, na);
-  else hipLaunchKernelGGL(resize_v_norm_kernel<bf16_t>, dim3(gv), dim3(256), 0, st, (const uint8_t*)mid, (bf16_t*)out, (const int*)bounds_v, (const int*)kk_v, Hin, C, S, kv, na);
+  DGTD_DISPATCH(out_dt, hipLaunchKernelGGL(resize_v_norm_kernel<T_>, dim3(gv), dim3(256), 0, st, (const uint8_t*)mid, (T_*)out, (const int*)bounds_v, (const int*)kk_v, Hin, C, S,
+                                           kv, na));
   DGTD_CHECK_LAUNCH("preprocess_vertical");
   return 0;
 }

@@ -245,13 +245,10 @@ extern "C" int dgtd_sam_fwd(const void* xh, const void* xl, const float* w1, con
   const hipStream_t st = (hipStream_t)s;
   const int V = DGTD_IS_HALF(dt) ? 8 : 4, gx = slices(HW, C), ax = apply_slices(HW, C / V);
   float* partial = stats + sam_stats_floats(B, C, R);
-  if (dt == DGTD_F16) hipLaunchKernelGGL((sam_pool_kernel<f16_t, false>), dim3(gx, B, 2), dim3(256), 0, st, (const f16_t*)xh, (const f16_t*)xl, (const f16_t*)nullptr, partial, HW, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL((sam_pool_kernel<bf16_t, false>), dim3(gx, B, 2), dim3(256), 0, st, (const bf16_t*)xh, (const bf16_t*)xl, (const bf16_t*)nullptr, partial, HW, C);
-  else hipLaunchKernelGGL((sam_pool_kernel<float, false>), dim3(gx, B, 2), dim3(256), 0, st, (const float*)xh, (const float*)xl, (const float*)nullptr, partial, HW, C);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL((sam_pool_kernel<T_, false>), dim3(gx, B, 2), dim3(256), 0, st, (const T_*)xh, (const T_*)xl, (const T_*)nullptr, partial, HW, C));
   DGTD_CHECK_LAUNCH("sam_pool");
-  if (dt == DGTD_F16) hipLaunchKernelGGL(sam_apply_kernel<f16_t>, dim3(ax, B), dim3(256), 0, st, (const f16_t*)xh, (const f16_t*)xl, (const float*)partial, gx, w1, w2, v1, v2, stats, (f16_t*)out, HW, C, R);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(sam_apply_kernel<bf16_t>, dim3(ax, B), dim3(256), 0, st, (const bf16_t*)xh, (const bf16_t*)xl, (const float*)partial, gx, w1, w2, v1, v2, stats, (bf16_t*)out, HW, C, R);
-  else hipLaunchKernelGGL(sam_apply_kernel<float>, dim3(ax, B), dim3(256), 0, st, (const float*)xh, (const float*)xl, (const float*)partial, gx, w1, w2, v1, v2, stats, (float*)out, HW, C, R);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(sam_apply_kernel<T_>, dim3(ax, B), dim3(256), 0, st, (const T_*)xh, (const T_*)xl, (const float*)partial, gx, w1, w2, v1, v2, stats,
+                                       (T_*)out, HW, C, R));
   DGTD_CHECK_LAUNCH("sam_apply");
   return 0;
 }
@@ -263,13 +260,10 @@ extern "C" int dgtd_sam_bwd(const void* g, const void* xh, const void* xl, const
   DGTD_REQUIRE(sam_ok(B, HW, C, R, dt), "sam_bwd: unsupported sizes B=%d HW=%d C=%d R=%d dtype %d", B, HW, C, R, (int)dt);
   const hipStream_t st = (hipStream_t)s;
   const int V = DGTD_IS_HALF(dt) ? 8 : 4, gx = slices(HW, C), ax = apply_slices(HW, C / V);
-  if (dt == DGTD_F16) hipLaunchKernelGGL((sam_pool_kernel<f16_t, true>), dim3(gx, B, 2), dim3(256), 0, st, (const f16_t*)xh, (const f16_t*)xl, (const f16_t*)g, scratch, HW, C);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL((sam_pool_kernel<bf16_t, true>), dim3(gx, B, 2), dim3(256), 0, st, (const bf16_t*)xh, (const bf16_t*)xl, (const bf16_t*)g, scratch, HW, C);
-  else hipLaunchKernelGGL((sam_pool_kernel<float, true>), dim3(gx, B, 2), dim3(256), 0, st, (const float*)xh, (const float*)xl, (const float*)g, scratch, HW, C);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL((sam_pool_kernel<T_, true>), dim3(gx, B, 2), dim3(256), 0, st, (const T_*)xh, (const T_*)xl, (const T_*)g, scratch, HW, C));
   DGTD_CHECK_LAUNCH("sam_dgate_sum");
-  if (dt == DGTD_F16) hipLaunchKernelGGL(sam_bwd_kernel<f16_t>, dim3(ax, B), dim3(256), 0, st, (const f16_t*)g, (const float*)scratch, gx, stats, w1, w2, v1, v2, (f16_t*)dxh, (f16_t*)dxl, dw, HW, C, R);
-  else if (dt == DGTD_BF16) hipLaunchKernelGGL(sam_bwd_kernel<bf16_t>, dim3(ax, B), dim3(256), 0, st, (const bf16_t*)g, (const float*)scratch, gx, stats, w1, w2, v1, v2, (bf16_t*)dxh, (bf16_t*)dxl, dw, HW, C, R);
-  else hipLaunchKernelGGL(sam_bwd_kernel<float>, dim3(ax, B), dim3(256), 0, st, (const float*)g, (const float*)scratch, gx, stats, w1, w2, v1, v2, (float*)dxh, (float*)dxl, dw, HW, C, R);
+  DGTD_DISPATCH(dt, hipLaunchKernelGGL(sam_bwd_kernel<T_>, dim3(ax, B), dim3(256), 0, st, (const T_*)g, (const float*)scratch, gx, stats, w1, w2, v1, v2, (T_*)dxh, (T_*)dxl,
+                                       dw, HW, C, R));
   DGTD_CHECK_LAUNCH("sam_bwd");
   return 0;
 }

@@ -240,7 +240,8 @@ def test_prelu_shared_slope(dgtd, shape, dtype, channels_last):
     torch.testing.assert_close(ha, ga, atol=1e-3 * math.sqrt(x.numel()) * (1 if dtype == torch.float32 else 30), rtol=1e-4 if dtype == torch.float32 else 2e-2)
 
 
-@pytest.mark.parametrize("B,C,H,W", [(2, 32, 16, 16), (3, 64, 12, 20), (2, 96, 64, 64), (1, 64, 128, 128)])
+# B = 33 is the smallest batch beyond the fused backward kernel (CA_MAXB = 32, csrc/hitnet_glue.hip): the two-kernel backward
+@pytest.mark.parametrize("B,C,H,W", [(2, 32, 16, 16), (3, 64, 12, 20), (2, 96, 64, 64), (1, 64, 128, 128), (33, 32, 8, 8)])
 @pytest.mark.parametrize("dtype", DTYPES, ids=str)
 def test_ca_gate_matches_calayer_plus_residual(dgtd, B, C, H, W, dtype):
     """CALayer (cod.py:415-431) + the CAB residual (cod.py:451) against the plain torch composition in fp32."""
@@ -619,6 +620,30 @@ def test_dwconv_benchmarked_shapes_vs_fp32_torch(dgtd, K, gelu, B, H, W, C, half
     assert (hw.float() - gw).norm() / gw.norm() < 2e-2, "weight gradient"
     assert (hb.float() - gb).norm() / gb.norm() < 2e-2, "bias gradient"
     torch.testing.assert_close(hw.float(), gw, atol=3e-2 * math.sqrt(n), rtol=5e-2)
+
+
+# the direct depthwise kernels, which the shape alone selects: 7x7 when C % 128 != 0, 3x3 when H < 8 (K, B, H, W, C)
+DW_DIRECT = [(7, 2, 9, 10, 64), (3, 2, 5, 6, 64)]
+
+
+@pytest.mark.parametrize("K,B,H,W,C", DW_DIRECT, ids=[f"k{s[0]}_{s[1]}x{s[2]}x{s[3]}x{s[4]}" for s in DW_DIRECT])
+@pytest.mark.parametrize("gelu", [False, True])
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_dwconv_direct_forward_vs_fp32_torch(dgtd, K, B, H, W, C, gelu, dtype):
+    """dgtd_dwconv_fwd modes 0/1 on the direct strip kernel (dwconv_fwd_kernel), forward only (the weight gradient needs C % 128 == 0),
+    against fp32 F.conv2d (+ exact erf GELU) on the same rounded inputs."""
+    x = _rand(B, H, W, C, seed=1, dtype=dtype)
+    w = (_rand(C, 1, K, K, seed=2) / K).to(dtype)
+    b = (0.1 * _rand(C, seed=3)).to(dtype)
+    ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.float(), b.float(), padding=K // 2, groups=C).permute(0, 2, 3, 1)
+    ref = F.gelu(ref) if gelu else ref
+    with torch.no_grad():
+        y = dgtd.ops.dwconv_nhwc(x, w, b, gelu)
+    assert y.dtype == dtype and y.shape == x.shape
+    if dtype == torch.float32:
+        torch.testing.assert_close(y, ref, atol=1e-4, rtol=1e-4)
+    else:
+        torch.testing.assert_close(y.float(), ref, atol=3e-2, rtol=2e-2)
 
 
 DWB = [(7, 5, 8, 32, 32, 512), (7, 3, 2, 20, 12, 256), (3, 4, 2, 16, 16, 1024), (7, 35, 1, 9, 8, 128)]
