@@ -164,30 +164,9 @@ def check_cuda(*ts: torch.Tensor) -> None:
             raise DgtdError("dgtd ops need contiguous tensors")
 
 
-class Profiler:
-    """HIP-event timing of every C-ABI launch on the stream it is launched on (bench.py's roofline leg).
-    ``algo`` = (bound, amount): algorithmic HBM bytes or MFMA flops of that launch."""
-
-    def __init__(self):
-        self.records = []  # (key, start_event, stop_event, bound, amount)
-
-    def summary(self):
-        torch.cuda.synchronize()
-        out = {}
-        for key, a, b, bound, amount in self.records:
-            e = out.setdefault(key, {"calls": 0, "ms": 0.0, "amount": 0.0, "bound": bound})
-            e["calls"] += 1
-            e["ms"] += a.elapsed_time(b)
-            e["amount"] += amount
-        return out
-
-
-PROFILER = None
-
-
 def profile_native(on: bool) -> None:
-    """Per-call device timing INSIDE libdgtd.so (dgtd_profile_enable): unlike ``PROFILER`` above it sees the calls of both host binding
-    layers, i.e. the very autograd nodes the timed training step runs (C++ bindings included)."""
+    """Per-call device timing INSIDE libdgtd.so (dgtd_profile_enable): it sees the calls of both host binding layers, i.e. the very
+    autograd nodes the timed training step runs (C++ bindings included)."""
     load().dgtd_profile_enable(1 if on else 0)
 
 
@@ -210,17 +189,9 @@ def profile_native_summary() -> dict:
     return out
 
 
-def call(name: str, *args, algo=None, key=None):
+def call(name: str, *args):
     lib = load()
-    prof = PROFILER
-    if prof is not None:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
     rc = getattr(lib, name)(*args)
-    if prof is not None:
-        b.record()
-        bound, amount = algo if algo is not None else ("hbm", 0.0)
-        prof.records.append((key or name, a, b, bound, float(amount)))
     if rc != 0:
         raise DgtdError(f"{name} failed (code {rc}): {lib.dgtd_last_error().decode()}")
 

@@ -4,7 +4,6 @@
 // training step is host-bound in eager Python (~1600 Python autograd.Function calls per step); these nodes cost a few microseconds.
 #include <ATen/ATen.h>
 #include <atomic>
-#include <cstdlib>
 #include <algorithm>
 #include <map>
 #include <set>
@@ -12,8 +11,6 @@
 #include <mutex>
 #include <vector>
 #include <c10/hip/HIPStream.h>
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPCachingAllocator.h>
 #include <torch/autograd.h>
 #include <torch/csrc/autograd/engine.h>
 #include <torch/library.h>
@@ -215,6 +212,11 @@ static bool own_wgrad_try(at::ScalarType dt, const void* dy, const void* x, void
                           int64_t s_x, int64_t s_dw, const at::TensorOptions& o);
 namespace dgemm_fwd { bool batched_dw(at::ScalarType dt, const void* dy, const void* x, void* dw, int64_t N, int64_t K, int64_t M, int batch, int64_t s_dy,
                                       int64_t s_x, int64_t s_dw, const at::TensorOptions& o); }
+// the most slices a long token dimension is cut into for a weight-gradient GEMM (flush_gemms and gemm_dw)
+inline int64_t wgrad_max_split() {
+  static const int64_t v = dgemm::env_int("DGTD_WGRAD_SPLIT", 32);
+  return v;
+}
 static void flush_gemms(std::vector<PendingGemm>& gs) {
   std::sort(gs.begin(), gs.end(), [](const PendingGemm& a, const PendingGemm& b) {
     return std::tie(a.group, a.which, a.idx) < std::tie(b.group, b.which, b.idx); });
@@ -236,8 +238,7 @@ static void flush_gemms(std::vector<PendingGemm>& gs) {
     // few layers with a long token dimension (3 blocks x 131072 tokens at stage 0): the batch alone does not fill the chip, so each
     // layer is additionally split along the tokens - the slots are dense, so (layer, split) is still ONE uniform stride - and the
     // bf16 partials are summed per layer (fp32 accumulation inside the reduction), as the per-layer path does
-    static const int64_t max_split = [] { const char* e = std::getenv("DGTD_WGRAD_SPLIT"); return e ? (int64_t)std::atol(e) : (int64_t)32; }();
-    int64_t S = n >= 16 ? 1 : std::min<int64_t>(max_split, a.M / 1024);
+    int64_t S = n >= 16 ? 1 : std::min<int64_t>(wgrad_max_split(), a.M / 1024);
     while (S > 1 && a.M % S) --S;
     const bool dense = n == 1 || (sx == a.M * a.K && sdy == a.M * a.N && sdw == a.N * a.K);
     // own kernel first when switched on (it splits the tokens itself, in fp32); everything below is the library path
@@ -306,10 +307,7 @@ constexpr int CA_MAX_CALLS = 8;
 // the last of those calls: the reducer switches them off when it gathers buckets from inside the backward pass (eager overlap mode).
 static std::atomic<bool> g_shared_ok{true};
 void set_shared_deferral(bool on) { g_shared_ok.store(on); }
-inline bool conv_defer_on() {
-  static const bool on = [] { const char* e = std::getenv("DGTD_DEFER_CONV3X3"); return !e || std::atoi(e) != 0; }();
-  return on && g_shared_ok.load(std::memory_order_relaxed);
-}
+inline bool conv_defer_on() { return g_shared_ok.load(std::memory_order_relaxed); }
 // forward: note that this weight runs with this geometry; returns whether the call may be deferred as far as the forward can tell
 inline bool conv_register(const Tensor& w_arg, const Tensor& w, const ConvKey& k) {
   if (!deferring() || !conv_defer_on()) return false;
@@ -395,61 +393,7 @@ static void flush_convs(std::vector<PendingConv>& cs, const std::map<const void*
 }
 
 static std::atomic<int64_t> g_flushed{0};
-// ASYNCHRONOUS FLUSH: the parked weight-gradient work is a handful of LARGE launches (batched GEMMs over 27 layers, batched depthwise
-// and 3x3 weight gradients: ~4.4 ms per step at config 2) that nothing in the backward pass waits for, while the backward pass itself
-// is a chain of small latency-bound launches that leave most of the chip idle.  flush_deferred_async() runs everything parked so far
-// on a SIDE stream forked from the caller's stream (event edges both ways, so it is captured into a hipGraph as a parallel branch);
-// the next synchronous flush - at the latest the end-of-backward callback - joins it.  The caller picks a point where no shared
-// deferral is half-way (dgtd.nn: when the gradient of the texture-diffuser embedding arrives, i.e. after the Hitnet decoder, every PVT
-// block and the prompt decoders have run backward, with the whole ConvNeXt trunk still to go).
-// Tensors the side stream reads are recorded on it (the caching allocator must not hand their memory to main-stream allocations
-// while the side stream is still running); the library-GEMM context is per stream (gemm.h).
-static c10::optional<c10::hip::HIPStream> g_side_stream;
-static hipEvent_t g_fork_event = nullptr, g_join_event = nullptr;     // plain HIP events (record / stream-wait are capturable)
-static bool g_async_outstanding = false;
-static thread_local const c10::hip::HIPStream* t_record_on = nullptr;
-inline void keep_for_side(const Tensor& t) {
-  if (t_record_on && t.defined() && t.has_storage() && t.is_cuda()) c10::hip::HIPCachingAllocator::recordStream(t.storage().data_ptr(), *t_record_on);
-}
-static void join_async() {
-  if (!g_async_outstanding) return;
-  TORCH_CHECK(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), g_join_event, 0) == hipSuccess, "dgtd: joining the side stream failed");
-  g_async_outstanding = false;
-}
-static void flush_deferred_impl();
 void flush_deferred() {
-  join_async();
-  flush_deferred_impl();
-}
-void flush_deferred_async() {
-  // measured at config 2 (profiles/r03_async_flush.txt): 31.13 ms/step with the side branch, 30.42 without - the chip-filling weight-gradient
-  // launches slow the latency-bound main chain down by more than they hide.  Kept behind DGTD_ASYNC_FLUSH=1 for other shapes.
-  static const bool on = [] { const char* e = std::getenv("DGTD_ASYNC_FLUSH"); return e && std::atoi(e) != 0; }();
-  if (!on) return;
-  {
-    std::lock_guard<std::mutex> lk(g_pending_mu);
-    if (g_pending.empty() && g_pending_dw.empty() && g_pending_gemm.empty() && g_pending_conv.empty() && g_ca_acc.empty()) return;
-  }
-  join_async();                                     // one side branch at a time
-  const auto cur = c10::hip::getCurrentHIPStream();
-  if (!g_side_stream || g_side_stream->device_index() != cur.device_index()) g_side_stream = c10::hip::getStreamFromPool(false, cur.device_index());
-  if (!g_fork_event) {
-    TORCH_CHECK(hipEventCreateWithFlags(&g_fork_event, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&g_join_event, hipEventDisableTiming) == hipSuccess, "dgtd: hipEventCreate failed");
-  }
-  // the side stream sees everything enqueued so far (partials, saved activations)
-  TORCH_CHECK(hipEventRecord(g_fork_event, cur.stream()) == hipSuccess && hipStreamWaitEvent(g_side_stream->stream(), g_fork_event, 0) == hipSuccess,
-              "dgtd: forking the side stream failed");
-  {
-    c10::hip::HIPStreamGuard guard(*g_side_stream);
-    t_record_on = &*g_side_stream;
-    try { flush_deferred_impl(); } catch (...) { t_record_on = nullptr; throw; }
-    t_record_on = nullptr;
-  }
-  TORCH_CHECK(hipEventRecord(g_join_event, g_side_stream->stream()) == hipSuccess, "dgtd: recording the join event failed");
-  g_async_outstanding = true;
-}
-static void flush_deferred_impl() {
   {
     std::vector<PendingConv> convs;
     std::map<const void*, ConvDest> dest;
@@ -461,7 +405,6 @@ static void flush_deferred_impl() {
       g_conv_flip.clear();
     }
     g_flushed += (int64_t)convs.size();
-    for (auto& c : convs) { keep_for_side(c.x); keep_for_side(c.dy); keep_for_side(c.mask); }
     if (!convs.empty()) flush_convs(convs, dest);
   }
   std::vector<PendingReduce> todo;
@@ -471,7 +414,6 @@ static void flush_deferred_impl() {
     std::lock_guard<std::mutex> lk(g_pending_mu);
     gemms.swap(g_pending_gemm);
   }
-  for (auto& gm : gemms) { keep_for_side(gm.x); keep_for_side(gm.dy); }
   if (!gemms.empty()) flush_gemms(gemms);
   {
     std::lock_guard<std::mutex> lk(g_pending_mu);
@@ -485,12 +427,9 @@ static void flush_deferred_impl() {
   }
   for (auto& kv : cas) {
     CaAcc& a = kv.second;
-    keep_for_side(a.buf);
     todo.push_back(PendingReduce{dgtd_reduce_entry{a.buf.data_ptr<float>(), a.count * a.rows, 2 * a.rc, (float*)a.out1, a.rc, a.out2, (int32_t)DGTD_F32, 0, 0, nullptr}, a.buf});
   }
   g_flushed += (int64_t)(gemms.size() + todo.size() + dws.size());
-  for (auto& p : todo) keep_for_side(p.ws);
-  for (auto& d : dws) { keep_for_side(d.x); keep_for_side(d.du); }
   if (todo.empty() && dws.empty()) return;
   std::vector<dgtd_reduce_entry> es;
   es.reserve(todo.size() + dws.size());
@@ -529,10 +468,6 @@ static void flush_deferred_impl() {
 // Entries die with the weight's storage (weak reference); outside zero_grad() .. finish() the nodes pack on the fly as before.
 struct PreparedDw { c10::weak_intrusive_ptr<c10::StorageImpl> wstore; const void* w; const void* b; Tensor packed; int C, K; at::ScalarType dt; };
 static std::map<const void*, PreparedDw> g_prepared_dw;
-inline bool prepare_on() {
-  static const bool on = [] { const char* e = std::getenv("DGTD_PREPARE_WEIGHTS"); return !e || std::atoi(e) != 0; }();
-  return on;
-}
 static void refresh_prepared() {
   std::map<int, std::vector<PreparedDw*>> by_dt;
   {
@@ -554,7 +489,7 @@ static void refresh_prepared() {
 // the packed weights of (weight, bias) for this step: the registered buffer (already refreshed), or a fresh pack that is registered
 inline Tensor packed_dw(const Tensor& weight, const Tensor& bias, bool has_bias, int64_t C, int64_t K) {
   const int64_t KK = K * K;
-  const bool use = deferring() && prepare_on() && weight.has_storage();
+  const bool use = deferring() && weight.has_storage();
   if (use) {
     std::lock_guard<std::mutex> lk(g_pending_mu);
     auto it = g_prepared_dw.find(weight.data_ptr());
@@ -597,7 +532,7 @@ void set_deferred(bool on) {
     flush_deferred();
   }
   g_defer.store(on);
-  if (on && prepare_on()) refresh_prepared();
+  if (on) refresh_prepared();
   if (on && own_gemm_on()) refresh_transposed();
 }
 int64_t flushed_reductions() { return g_flushed.load(); }    // cumulative number of parked entries that flush_deferred() has served
@@ -746,8 +681,7 @@ struct SraAttnFn : public torch::autograd::Function<SraAttnFn> {
 // with the other column reductions of the backward pass when the reducer has switched deferral on.
 inline void dwconv_weight_grads(const Tensor& x, const Tensor& du, bool has_bias, int64_t C, int64_t K, Tensor& dw, Tensor& db, bool defer) {
   const int64_t KK = K * K;
-  static const bool batch_dw = [] { const char* e = std::getenv("DGTD_DEFER_DWCONV"); return !e || std::atoi(e) != 0; }();
-  if (defer && batch_dw && C % 128 == 0) { park_dw(x, du, dw, db, has_bias, (int)C, (int)K); return; }   // the batched kernel walks 128-channel groups
+  if (defer && C % 128 == 0) { park_dw(x, du, dw, db, has_bias, (int)C, (int)K); return; }   // the batched kernel walks 128-channel groups
   Tensor ws = at::empty({dgtd_dwconv_bwd_weight_workspace((int)x.size(0), (int)x.size(1), (int)x.size(2), (int)C, (int)K) / 4}, x.options().dtype(at::kFloat));
   int nb = 0;
   check(dgtd_dwconv_bwd_weight_partial(x.data_ptr(), du.data_ptr(), has_bias ? 1 : 0, ws.data_ptr(), (int)x.size(0), (int)x.size(1), (int)x.size(2),
@@ -913,7 +847,7 @@ Tensor colsum(const Tensor& x2, at::ScalarType out_dt, bool defer) {
 // ------------------------------------------------------------------------------------------------ the package's own MFMA GEMM (csrc/gemm.hip)
 // DGTD_OWN_GEMM=0 keeps every Linear on the library GEMM (A/B switch).  Shapes outside the kernel (M % 128, N % 64, K % 64) always do.
 inline bool own_gemm_on() {
-  static const bool on = [] { const char* e = std::getenv("DGTD_OWN_GEMM"); return !e || std::atoi(e) != 0; }();
+  static const bool on = dgemm::env_int("DGTD_OWN_GEMM", 1) != 0;
   return on;
 }
 inline bool aligned16(const Tensor& t) { return ((uintptr_t)t.data_ptr() & 15) == 0; }
@@ -1011,7 +945,7 @@ inline Tensor gemm_dx(const Tensor& dy2, const Tensor& wc) {                    
 // later (tests, tools/bench_wgrad_own.py).  When on, flush_gemms and gemm_dw try dgtd_gemm_wgrad_batched first and keep the library path
 // for what dgtd_gemm_wgrad_supported refuses (a token count that is no multiple of 64, fp32, unaligned or overlapping slots).  The
 // two counters tell a test which way the calls went.
-static std::atomic<bool> g_own_wgrad{[] { const char* e = std::getenv("DGTD_OWN_WGRAD"); return e && std::atoi(e) != 0; }()};
+static std::atomic<bool> g_own_wgrad{dgemm::env_int("DGTD_OWN_WGRAD", 0) != 0};
 static std::atomic<int64_t> g_own_wgrad_calls{0}, g_own_wgrad_fallbacks{0};
 inline bool own_wgrad_on() { return g_own_wgrad.load(std::memory_order_relaxed); }
 void set_own_wgrad(bool on) { g_own_wgrad.store(on); }
@@ -1045,8 +979,7 @@ Tensor gemm_dw(const Tensor& dy2, const Tensor& x2) {                           
     Tensor dw = at::empty({N, K}, dy2.options());
     if (own_wgrad_try(dy2.scalar_type(), dy2.data_ptr(), x2.data_ptr(), dw.data_ptr(), M, N, K, 1, 0, 0, 0, dy2.options())) return dw;
   }
-  static const int64_t max_split = [] { const char* e = std::getenv("DGTD_WGRAD_SPLIT"); return e ? (int64_t)std::atol(e) : (int64_t)32; }();
-  const int64_t S = std::min<int64_t>(max_split, M / 1024);
+  const int64_t S = std::min<int64_t>(wgrad_max_split(), M / 1024);
   if (S >= 4 && M % S == 0 && is16(dy2.scalar_type())) {
     Tensor part = at::empty({S, N, K}, dy2.options());
     if (!(bf && dgemm::matmul_16(dy2.scalar_type(), dy2.data_ptr(), x2.data_ptr(), part.data_ptr(), nullptr, N, K, M / S, true, false, (int)S, (M / S) * N,
@@ -1926,7 +1859,6 @@ TORCH_LIBRARY(dgtd, m) {
         "float momentum, float eps) -> Tensor", &batch_norm);
   m.def("set_deferred(bool on) -> ()", &set_deferred);
   m.def("flush_deferred() -> ()", &flush_deferred);
-  m.def("flush_deferred_async() -> ()", &flush_deferred_async);
   m.def("pending_reductions() -> int", &pending_reductions);
   m.def("flushed_reductions() -> int", &flushed_reductions);
   m.def("wgrad_batched(Tensor dy, Tensor x) -> Tensor", &wgrad_batched);

@@ -9,10 +9,10 @@
 #include <hipblaslt/hipblaslt.h>
 #include <hipblaslt/hipblaslt-ext.hpp>
 
-#include <vector>
-
+#include <algorithm>
 #include <cstdlib>
 #include <unordered_map>
+#include <vector>
 
 namespace dgemm {
 
@@ -48,28 +48,26 @@ struct Ctx {
 };
 constexpr size_t kWorkspace = 64u << 20;
 
-inline bool enabled() {
-  static const bool on = [] { const char* e = std::getenv("DGTD_DIRECT_GEMM"); return !(e && e[0] == '0'); }();
-  return on;
-}
+// the host layer's switches and tuning knobs: read once, into a function-local `static const` (the counterpart of csrc/common.h env_int)
+inline long env_int(const char* name, long dflt) { const char* e = std::getenv(name); return e ? std::atol(e) : dflt; }
 
 // Pick among the heuristic's first candidates by measurement when a plan is created (once per shape and thread).  With the step
 // replayed as a hipGraph (GPU-bound) this is worth 0.7 ms of 33.4 per step at config 2 (245 vs 240 images/s); in the host-bound eager
 // step of round 1 it showed nothing.  DGTD_GEMM_TUNE=0 takes the heuristic's first answer.
 inline bool tune() {
-  static const bool on = [] { const char* e = std::getenv("DGTD_GEMM_TUNE"); return !(e && e[0] == '0'); }();
+  static const bool on = env_int("DGTD_GEMM_TUNE", 1) != 0;
   return on;
 }
 
 // DGTD_GEMM_EXHAUSTIVE=1: time EVERY library solution that supports the problem instead of the heuristic's first candidates
 // (hipblaslt_ext::getAllAlgos; hundreds per plan, seconds per shape - an offline-tuning switch, off by default)
 inline bool exhaustive() {
-  static const bool on = [] { const char* e = std::getenv("DGTD_GEMM_EXHAUSTIVE"); return e && e[0] == '1'; }();
+  static const bool on = env_int("DGTD_GEMM_EXHAUSTIVE", 0) != 0;
   return on;
 }
 
-// One context (handle, plan cache, 64 MB workspace) per thread AND stream: the deferred weight-gradient phase can run on a side stream
-// beside the backward pass (bindings.cpp flush_deferred_async); two GEMMs in flight on different streams must not share a workspace.
+// One context (handle, plan cache, 64 MB workspace) per thread AND stream: the step is captured on a stream of its own while warm-up and
+// evaluation run on the default stream; two GEMMs in flight on different streams must not share a workspace.
 inline Ctx& ctx(hipStream_t st) {   // never destroyed: a thread_local destructor could run after the HIP runtime has shut down
   thread_local std::unordered_map<hipStream_t, Ctx*>* m = new std::unordered_map<hipStream_t, Ctx*>();
   auto it = m->find(st);
@@ -88,7 +86,6 @@ inline void set_batch(hipblasLtMatrixLayout_t l, int32_t batch, int64_t stride) 
 // Returns false when hipBLASLt offers no algorithm for the problem: the caller then uses the ATen GEMM.
 inline bool matmul_16(at::ScalarType half_type, const void* A, const void* B, void* D, const void* bias, int64_t M, int64_t N, int64_t K,
                       bool transA, bool transB, int batch, int64_t sA, int64_t sB, int64_t sD, const at::TensorOptions& dev_opts, hipStream_t st) {
-  if (!enabled()) return false;
   const hipDataType DT = half_type == at::kHalf ? HIP_R_16F : HIP_R_16BF;
   Ctx& c = ctx(st);
   if (c.dead) return false;
@@ -127,7 +124,7 @@ inline bool matmul_16(at::ScalarType half_type, const void* A, const void* B, vo
     }
     if (good) {
       constexpr int kMaxTry = 32;
-      static const int kTry = [] { const char* e = std::getenv("DGTD_GEMM_CANDIDATES"); const int v = e ? std::atoi(e) : 32; return v < 1 ? 1 : (v > kMaxTry ? kMaxTry : v); }();
+      static const int kTry = (int)std::min(std::max(env_int("DGTD_GEMM_CANDIDATES", kMaxTry), 1L), (long)kMaxTry);
       hipblasLtMatmulHeuristicResult_t res[kMaxTry];
       int found = 0;
       // a plan first needed while the stream is being captured cannot be timed (event synchronisation is illegal there): first answer

@@ -3,12 +3,11 @@ trunks, so LayerNorm, attention and the depthwise convs see contiguous channel r
 NCHW<->NHWC permute copies exist on the path; strided k==s convolutions (ConvNeXt stem/downsample,
 the attention spatial-reduction conv) are patchify + GEMM.
 
-Reference citations are to /root/reference/twig/model/cod.py.
+Reference citations are to the reference's twig/model/cod.py.
 """
 from __future__ import annotations
 
 import math
-import os
 from typing import List, Optional
 
 import torch
@@ -18,8 +17,6 @@ import torch.nn.functional as F
 from .. import ops
 
 LATENT = 24
-# A/B switches for tools/ and bench runs (default: every native path on)
-_USE = {k: os.environ.get("DGTD_" + k.upper(), "1") != "0" for k in ("bilinear", "conv3x3", "cab_glue", "fused_linear", "ln_fork", "conv_gemm", "mlp_fused", "async_flush", "cab_node", "batchnorm", "sam_node")}
 
 
 # ------------------------------------------------------------------------------------------------ helpers
@@ -66,7 +63,7 @@ class Conv2d(nn.Conv2d):
 
     def forward(self, x):
         w, b = wb(self)
-        if (x.is_cuda and _USE["conv_gemm"] and self.groups == 1 and self.dilation == (1, 1) and self.kernel_size[0] == self.kernel_size[1]
+        if (x.is_cuda and self.groups == 1 and self.dilation == (1, 1) and self.kernel_size[0] == self.kernel_size[1]
                 and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1] and isinstance(self.padding[0], int)
                 and self.padding_mode == "zeros"):
             return ops.conv2d_gemm(x, w, b, self.stride[0], self.padding[0])      # patch gather + library GEMM, no MIOpen
@@ -153,7 +150,7 @@ class OverlapPatchEmbed(nn.Module):
         self.apply(_init_weights)
 
     def forward(self, x):
-        if x.is_cuda and _USE["conv_gemm"]:
+        if x.is_cuda:
             # patch gather straight from the producer's layout (NCHW fp32 image or channels_last map; the 16-bit cast of the image
             # happens inside the gather) + one GEMM: the result already is the token matrix
             t, H, W = ops.conv2d_tokens(x, *wb(self.proj), self.stride, self.patch_size // 2)
@@ -251,15 +248,13 @@ class Block(nn.Module):
         return self.drop_path.scale(x.shape[0], x.device) if isinstance(self.drop_path, DropPath) else None
 
     def forward(self, x, H, W, run=ops.NO_RUN):
-        if _USE["fused_linear"] and x.is_cuda:   # projection / fc2 + DropPath + residual as one node (bias gradient fused in its backward)
-            run.roles(out=0)                      # norm1 output = input of q (and of kv without spatial reduction)
-            v, xs = self.norm1.fork(x) if _USE["ln_fork"] else (self.norm1(x), x)
-            x = ops.linear_residual(self.attn.core(v, H, W, run), *wb(self.attn.proj), xs, self._scale(x))
-            run.roles(out=3)                      # norm2 output = input of fc1
-            v, xs = self.norm2.fork(x) if _USE["ln_fork"] else (self.norm2(x), x)
-            return ops.linear_residual(self.mlp.hidden(v, H, W, run), *wb(self.mlp.fc2), xs, self._scale(x))
-        x = ops.scale_residual(x, self.attn(self.norm1(x), H, W), self._scale(x))   # x + DropPath(attn), one pass
-        return ops.scale_residual(x, self.mlp(self.norm2(x), H, W), self._scale(x))
+        # projection / fc2 + DropPath + residual as one node each (bias gradient fused in its backward)
+        run.roles(out=0)                          # norm1 output = input of q (and of kv without spatial reduction)
+        v, xs = self.norm1.fork(x)
+        x = ops.linear_residual(self.attn.core(v, H, W, run), *wb(self.attn.proj), xs, self._scale(x))
+        run.roles(out=3)                          # norm2 output = input of fc1
+        v, xs = self.norm2.fork(x)
+        return ops.linear_residual(self.mlp.hidden(v, H, W, run), *wb(self.mlp.fc2), xs, self._scale(x))
 
 
 # ------------------------------------------------------------------------------------------------ diffuser
@@ -277,18 +272,13 @@ class convnext_Block(nn.Module):
 
     def forward_nhwc(self, x, run=ops.NO_RUN):
         s = self.drop_path.scale(x.shape[0], x.device) if isinstance(self.drop_path, DropPath) else None
-        if _USE["fused_linear"] and x.is_cuda:   # pwconv1+GELU and pwconv2+gamma+DropPath+residual as two nodes with fused backward passes
-            y, xs = ops.dwconv_fork(x, *wb(self.dwconv)) if _USE["ln_fork"] else (ops.dwconv_nhwc(x, *wb(self.dwconv)), x)
-            run.roles(out=0)                      # LayerNorm output = input of pwconv1 (deferred Linear 0 of the block)
-            y = self.norm(y)
-            run.roles(out=1)                      # GELU output = input of pwconv2 (deferred Linear 1)
-            if _USE["mlp_fused"]:                 # both Linears + GELU + layer scale + DropPath + residual: one node on the package's own GEMM
-                return ops.mlp_residual(y, *wb(self.pwconv1), *wb(self.pwconv2), xs, s, self.gamma)
-            h = ops.linear_gelu(y, *wb(self.pwconv1))
-            return ops.linear_residual(h, *wb(self.pwconv2), xs, s, self.gamma)
-        y = ops.dwconv_nhwc(x, *wb(self.dwconv))
-        y = self.pwconv2(F.gelu(self.pwconv1(self.norm(y))))
-        return ops.scale_residual(x, y, s, self.gamma)   # x + DropPath(gamma * y) in one pass
+        y, xs = ops.dwconv_fork(x, *wb(self.dwconv))
+        run.roles(out=0)                          # LayerNorm output = input of pwconv1 (deferred Linear 0 of the block)
+        y = self.norm(y)
+        run.roles(out=1)                          # GELU output = input of pwconv2 (deferred Linear 1)
+        # both Linears + GELU + layer scale + DropPath + residual: one node on the package's own GEMM where the shape fits it,
+        # else pwconv1+GELU and pwconv2+gamma+DropPath+residual as two nodes with fused backward passes
+        return ops.mlp_residual(y, *wb(self.pwconv1), *wb(self.pwconv2), xs, s, self.gamma)
 
     def forward(self, x):  # reference contract: NCHW in, NCHW out
         return self.forward_nhwc(x.permute(0, 2, 3, 1).contiguous()).permute(0, 3, 1, 2)
@@ -343,7 +333,7 @@ class ShapePropEncoder(nn.Module):
             y = _tokens_to_nchw(ops.linear(t, cw.flatten(1), cb), h, w)
             if (h, w) == size:
                 taps.append(y)                                   # bilinear resize to the same size is the identity
-            elif _USE["bilinear"] and y.is_cuda and y.shape[1] % (16 // y.element_size()) == 0:
+            elif y.is_cuda and y.shape[1] % (16 // y.element_size()) == 0:
                 taps.append(ops.bilinear_resize(y, size[0], size[1], False))
             else:
                 taps.append(F.interpolate(y, size=size, mode="bilinear", align_corners=False))
@@ -448,16 +438,16 @@ class ShapePropDecoder(nn.Module):
         Hin = h.shape[-2]
         s_ = Hin // H
         if s_ == 1:
-            if _USE["conv3x3"] and w.dtype == h.dtype and ops.conv3x3_ops.supported(h, w.shape[1], w.shape[0], Hin, h.shape[-1]):
+            if w.dtype == h.dtype and ops.conv3x3_ops.supported(h, w.shape[1], w.shape[0], Hin, h.shape[-1]):
                 y = ops.conv3x3(h, w, b)                # stage-1 prompts (24 -> 64 at S/4): same kernel as the trunk layers
-            elif h.is_cuda and _USE["conv_gemm"]:
+            elif h.is_cuda:
                 return ops.conv2d_tokens(h, w, b, 1, 1)[0]
             else:
                 y = F.conv2d(h, w, b, padding=1)
         elif s_ in (2, 4, 8) and Hin == H * s_ and h.shape[-1] == W * s_:
             w4 = _fold_2x2_mean(w)                 # mean of the four shifted 3x3 kernels (zero padded), one launch
             off = s_ // 2 - 2                      # first input row/col of the 4x4 window of output 0
-            if h.is_cuda and _USE["conv_gemm"]:
+            if h.is_cuda:
                 # the offset window grid is a strided view the patch gather reads directly (s_ = 4: the windows tile the map)
                 src, pad = (h, -off) if off < 0 else (h[:, :, off:, off:], 0)
                 t, Ht, Wt = ops.conv2d_tokens(src, w4, b, s_, pad)
@@ -546,13 +536,6 @@ class PyramidVisionTransformerImpr(nn.Module):
         embedding1, embedding3 = self.prompt_encoder(image, depth, x_hp=x_hp)
         embedding3 = embedding3.contiguous(memory_format=torch.channels_last)
         ops.mark_flush_point(embedding3)       # backward: Hitnet decoder, all PVT blocks and the prompt decoders are done at this gradient
-        if _USE["async_flush"] and embedding3.requires_grad and embedding3.is_cuda:
-            # backward: when this gradient arrives, the Hitnet decoder, every PVT block and the prompt decoders are done and the whole
-            # ConvNeXt trunk is still to go - their parked weight-gradient work (batched GEMMs, depthwise / 3x3 weight gradients) starts
-            # on a side stream now and runs beside the ConvNeXt backward pass instead of after it (bindings.cpp flush_deferred_async)
-            nat = ops._native.ops()
-            if nat is not None:
-                embedding3.register_hook(_async_flush_hook)
         trunks, off = self._prompt_trunks(embedding3), 0
         outs = []
         for i in range(4):
@@ -578,7 +561,7 @@ class PyramidVisionTransformerImpr(nn.Module):
         c0, c1 = [d.decoder[0] for d in decs], [d.decoder[2] for d in decs]
         w0 = [wb(c)[0] for c in c0]
         B, C, H, W = embedding.shape
-        if not (_USE["conv3x3"] and ops.conv3x3_ops.supported(embedding, C, C, H, W) and all(w.dtype == embedding.dtype for w in w0)):
+        if not (ops.conv3x3_ops.supported(embedding, C, C, H, W) and all(w.dtype == embedding.dtype for w in w0)):
             return None
         x = embedding.permute(0, 2, 3, 1).contiguous()
         h = ops.conv3x3_stack(x, w0, [wb(c)[1] for c in c0], True)
@@ -586,13 +569,6 @@ class PyramidVisionTransformerImpr(nn.Module):
 
     def forward(self, x, depth, x_hp=None):
         return self.forward_features(x, depth, x_hp)
-
-
-def _async_flush_hook(grad):
-    nat = ops._native.ops()
-    if nat is not None:
-        nat.flush_deferred_async()
-    return None
 
 
 def _pvt_variant(name, depths, mlp_ratios, doc):
@@ -624,14 +600,14 @@ class BasicConv2d(nn.Module):
 
     def _bn(self, t):
         """cod.py:366: the fused statistics + apply kernels (two launches each way) where they tile the map, torch's otherwise."""
-        if _USE["batchnorm"] and ops.batch_norm_supported(t, self.bn):
+        if ops.batch_norm_supported(t, self.bn):
             return ops.batch_norm(t, self.bn)
         return self.bn(t)
 
     def forward(self, x):
         c = self.conv
         w = wb(c)[0]
-        if (_USE["conv3x3"] and c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1)
+        if (c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1)
                 and w.dtype == x.dtype and ops.conv3x3_ops.supported(x, c.in_channels, c.out_channels, x.shape[2], x.shape[3])):
             return self._bn(ops.conv3x3(x, w))        # conv4 (96 -> 32 at S/8, cod.py:713): NHWC bf16 MFMA kernel
         if x.is_cuda and c.kernel_size == (1, 1) and c.stride == (1, 1) and c.padding == (0, 0):
@@ -665,22 +641,31 @@ class CAB(nn.Module):
         self.body = nn.Sequential(Conv2d(n_feat, n_feat, kernel_size, padding=pad, bias=bias), act,
                                   Conv2d(n_feat, n_feat, kernel_size, padding=pad, bias=bias))
 
+    def _conv3x3_ok(self, x):
+        c0, c1 = self.body[0], self.body[2]
+        return (c0.bias is None and c1.bias is None and wb(c0)[0].dtype == x.dtype
+                and ops.conv3x3_ops.supported(x, x.shape[1], x.shape[1], x.shape[2], x.shape[3]))
+
+    def composition(self, x):
+        """The block as separate ops, conv3x3 -> PReLU -> conv3x3 -> CA gate, for a device tensor, one shared PReLU slope and a
+        bias-free channel attention: what ``forward`` runs where ops.cab does not apply, and its reference in the tests."""
+        act, du = self.body[1], self.CA.conv_du
+        c0, c1 = self.body[0], self.body[2]
+        if self._conv3x3_ok(x):
+            res = ops.conv3x3(ops.prelu(ops.conv3x3(x, wb(c0)[0]), act.weight), wb(c1)[0])      # NHWC bf16 MFMA kernels
+        else:
+            res = c1(ops.prelu(c0(x), act.weight))
+        return ops.ca_gate(res, x, du[0].weight, du[2].weight)     # gate * res + x in three launches
+
     def forward(self, x):
         act, du = self.body[1], self.CA.conv_du
-        if _USE["cab_glue"] and x.is_cuda and isinstance(act, nn.PReLU) and act.weight.numel() == 1 and du[0].bias is None and du[2].bias is None:
-            c0, c1 = self.body[0], self.body[2]
-            w0, w1 = wb(c0)[0], wb(c1)[0]
-            if (_USE["conv3x3"] and c0.bias is None and c1.bias is None and w0.dtype == x.dtype
-                    and ops.conv3x3_ops.supported(x, x.shape[1], x.shape[1], x.shape[2], x.shape[3])):
-                if _USE["cab_node"]:             # the whole CAB as one node: PReLU (+ backward) and the skip gradient in conv epilogues
-                    out = ops.cab(x, w0, w1, act.weight, du[0].weight, du[2].weight)
-                    if out is not None:
-                        return out
-                res = ops.conv3x3(ops.prelu(ops.conv3x3(x, w0), act.weight), w1)      # NHWC bf16 MFMA kernels
-            else:
-                res = c1(ops.prelu(c0(x), act.weight))
-            return ops.ca_gate(res, x, du[0].weight, du[2].weight)     # gate * res + x in three launches
-        return self.CA(self.body(x)) + x
+        if not (x.is_cuda and isinstance(act, nn.PReLU) and act.weight.numel() == 1 and du[0].bias is None and du[2].bias is None):
+            return self.CA(self.body(x)) + x
+        if self._conv3x3_ok(x):                  # the whole CAB as one node: PReLU (+ backward) and the skip gradient in conv epilogues
+            out = ops.cab(x, wb(self.body[0])[0], wb(self.body[2])[0], act.weight, du[0].weight, du[2].weight)
+            if out is not None:
+                return out
+        return self.composition(x)
 
 
 class SAM(nn.Module):
@@ -701,7 +686,7 @@ class SAM(nn.Module):
         return x * (self.fc(y) * self.fc_wight(y)).to(x.dtype)[:, :, None, None]
 
     def forward(self, x_h, x_l):
-        if _USE["sam_node"] and x_h.is_cuda and x_l.shape == x_h.shape and ops.sam_supported(x_h, self.fc[0].weight.shape[0]):
+        if x_h.is_cuda and x_l.shape == x_h.shape and ops.sam_supported(x_h, self.fc[0].weight.shape[0]):
             return ops.sam(x_h, x_l, self.fc[0].weight, self.fc[2].weight, self.fc_wight[0].weight, self.fc_wight[2].weight)
         return self._gate(x_h) + self._gate(x_l)
 
@@ -722,7 +707,7 @@ class _SpatialAttention(nn.Module):  # cod.py:390-405; constructed (cod.py:704),
 def _up(x, scale, align):
     """Bilinear resize in the dtype of ``x``: under CUDA autocast the resampler would otherwise widen bf16 maps to fp32 and every
     consumer (cat, conv, CAB) would cast them back."""
-    if _USE["bilinear"] and x.is_cuda and x.shape[1] % (16 // x.element_size()) == 0:
+    if x.is_cuda and x.shape[1] % (16 // x.element_size()) == 0:
         return ops.bilinear_resize(x, int(math.floor(x.shape[2] * scale)), int(math.floor(x.shape[3] * scale)), align)
     if x.is_cuda and x.dtype != torch.float32:
         with torch.autocast("cuda", enabled=False):

@@ -1,7 +1,6 @@
 """Optional C++ autograd bindings (libdgtd_torch.so, csrc_torch/bindings.cpp) over the same C ABI.  They only remove Python
 overhead from the host-bound training step; kernels, numerics and error behaviour are those of libdgtd.so either way.  The Python
-autograd.Functions remain the reference binding and are used whenever the HIP-event profiler is active (bench.py roofline leg)
-or when DGTD_TORCH_BINDINGS=0."""
+autograd.Functions remain the reference binding, selected by DGTD_TORCH_BINDINGS=0 or by setting ENABLED to False."""
 from __future__ import annotations
 
 import os
@@ -17,9 +16,9 @@ _tried = False
 
 
 def ops():
-    """torch.ops.dgtd when the binding library is built and enabled and no profiler is attached, else None."""
+    """torch.ops.dgtd when the binding library is built and enabled, else None."""
     global _ops, _tried
-    if not ENABLED or L.PROFILER is not None:
+    if not ENABLED:
         return None
     if not _tried:
         _tried = True

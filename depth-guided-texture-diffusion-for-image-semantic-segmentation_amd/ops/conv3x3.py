@@ -28,18 +28,17 @@ class _Conv3x3Fn(Function):
         _, B, H, W, _ = x.shape
         y = torch.empty(Z, B, H, W, Co, dtype=x.dtype, device=x.device)
         bc = b.contiguous() if b is not None else None
-        flops = 2.0 * Z * B * H * W * 9 * Ci * Co
         L.call("dgtd_conv3x3_fwd", L.ptr(x), None, L.ptr(w), L.ptr(bc), L.ptr(y), Z, B, H, W, Ci, Co, int(relu), int(shared),
-               L.dtype_code(x), L.stream_ptr(), algo=("hbm", 2 * (x.numel() + y.numel())), key=f"dgtd_conv3x3_fwd[Z={Z},{H}x{W},{Ci}->{Co}]")
+               L.dtype_code(x), L.stream_ptr())
         ctx.save_for_backward(x, w, y if relu else None)
-        ctx.meta = (relu, shared, b is not None, flops)
+        ctx.meta = (relu, shared, b is not None)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
-        relu, shared, has_b, _ = ctx.meta
+        relu, shared, has_b = ctx.meta
         Z, Co, _, _, Ci = w.shape
         _, B, H, W, _ = x.shape
         dy = (dy if dy.dtype == x.dtype else dy.to(x.dtype)).contiguous()
@@ -49,16 +48,13 @@ class _Conv3x3Fn(Function):
             wt = torch.empty(Z, Ci, 3, 3, Co, dtype=w.dtype, device=w.device)
             L.call("dgtd_conv3x3_flip", L.ptr(w), L.ptr(wt), Z, Co, Ci, st)
             dx = torch.empty(Z, B, H, W, Ci, dtype=x.dtype, device=x.device)
-            L.call("dgtd_conv3x3_fwd", L.ptr(dy), L.ptr(y), L.ptr(wt), None, L.ptr(dx), Z, B, H, W, Co, Ci, 0, 0, L.dtype_code(dy), st,
-                   algo=("hbm", 2 * (dx.numel() + (2 if relu else 1) * dy.numel())), key=f"dgtd_conv3x3_bwd_x[Z={Z},{H}x{W},{Co}->{Ci}]")
+            L.call("dgtd_conv3x3_fwd", L.ptr(dy), L.ptr(y), L.ptr(wt), None, L.ptr(dx), Z, B, H, W, Co, Ci, 0, 0, L.dtype_code(dy), st)
             if shared:
                 dx = dx.sum(0, keepdim=True)
         dw = torch.empty_like(w)
         db = torch.empty(Z, Co, dtype=w.dtype, device=w.device) if has_b else None
         ws = torch.empty(L.load().dgtd_conv3x3_wgrad_workspace(Z, B, H, W, Ci, Co), dtype=torch.uint8, device=x.device)
-        L.call("dgtd_conv3x3_wgrad", L.ptr(x), L.ptr(dy), L.ptr(y), L.ptr(dw), L.ptr(db), L.ptr(ws), Z, B, H, W, Ci, Co, int(shared), L.dtype_code(x), st,
-               algo=("hbm", 2 * ((1 if shared else Z) * B * H * W * Ci + (2 if relu else 1) * dy.numel())),
-               key=f"dgtd_conv3x3_wgrad[Z={Z},{H}x{W},{Ci}->{Co}]")
+        L.call("dgtd_conv3x3_wgrad", L.ptr(x), L.ptr(dy), L.ptr(y), L.ptr(dw), L.ptr(db), L.ptr(ws), Z, B, H, W, Ci, Co, int(shared), L.dtype_code(x), st)
         return dx, dw, db, None
 
 

@@ -21,8 +21,7 @@ class _DiffuserFn(Function):
         L.check_cuda(x_hp, depth, rw, rb, ew, eb)
         B, _, S, _ = x_hp.shape
         x4 = torch.empty(B, LAT, 12, 12, dtype=torch.float32, device=x_hp.device)
-        L.call("dgtd_diffuser_fwd", L.ptr(x_hp), L.ptr(depth), L.ptr(rw), L.ptr(rb), L.ptr(ew), L.ptr(eb), L.ptr(x4), B, S,
-               L.stream_ptr(), algo=("hbm", 4.0 * B * (4 * P + LAT * P)))
+        L.call("dgtd_diffuser_fwd", L.ptr(x_hp), L.ptr(depth), L.ptr(rw), L.ptr(rb), L.ptr(ew), L.ptr(eb), L.ptr(x4), B, S, L.stream_ptr())
         ctx.save_for_backward(x_hp, depth, rw, rb, ew, eb)
         ctx.shapes = (reg_w.shape, enc_w.shape)
         return x4
@@ -49,8 +48,7 @@ class _DiffuseTailFn(Function):
         L.check_cuda(x4, image, w, b)
         B, _, S, _ = image.shape
         out = torch.empty_like(image)
-        L.call("dgtd_diffuse_tail_fwd", L.ptr(x4), L.ptr(w), L.ptr(b), L.ptr(image), L.ptr(out), B, S, L.stream_ptr(),
-               algo=("hbm", 2.0 * 4 * B * 3 * S * S))
+        L.call("dgtd_diffuse_tail_fwd", L.ptr(x4), L.ptr(w), L.ptr(b), L.ptr(image), L.ptr(out), B, S, L.stream_ptr())
         ctx.save_for_backward(x4, w)
         ctx.meta = (B, S, cw.shape)
         return out
@@ -65,8 +63,7 @@ class _DiffuseTailFn(Function):
         d_w = torch.zeros_like(w)
         d_b = torch.zeros(3, dtype=torch.float32, device=x4.device)
         ws = torch.empty(L.load().dgtd_diffuse_tail_bwd_workspace(B), dtype=torch.uint8, device=x4.device)
-        L.call("dgtd_diffuse_tail_bwd", L.ptr(gout), L.ptr(x4), L.ptr(w), L.ptr(g4), L.ptr(d_w), L.ptr(d_b), L.ptr(ws), B, S,
-               L.stream_ptr(), algo=("hbm", 4.0 * B * 3 * S * S))
+        L.call("dgtd_diffuse_tail_bwd", L.ptr(gout), L.ptr(x4), L.ptr(w), L.ptr(g4), L.ptr(d_w), L.ptr(d_b), L.ptr(ws), B, S, L.stream_ptr())
         return g4, d_w.view(wshape), d_b, None
 
 

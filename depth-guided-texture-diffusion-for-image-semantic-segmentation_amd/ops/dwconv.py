@@ -12,8 +12,7 @@ def _launch_fwd(x, wt_ptr, bias_ptr, aux, mode, K):
     B, H, W, C = x.shape
     y = torch.empty_like(x)
     L.call("dgtd_dwconv_fwd", L.ptr(x), wt_ptr, bias_ptr, L.ptr(aux), L.ptr(y), B, H, W, C, K, mode,
-           L.dtype_code(x), L.stream_ptr(), algo=("hbm", (3 if mode == 2 else 2) * x.element_size() * x.numel()),
-           key=f"dgtd_dwconv_fwd[k{K},mode{mode},{H}x{W}x{C}]")
+           L.dtype_code(x), L.stream_ptr())
     return y
 
 
@@ -53,8 +52,7 @@ class _DwConvFn(Function):
         ws = torch.empty(L.load().dgtd_dwconv_bwd_weight_workspace(B, H, W, C, K), dtype=torch.uint8, device=x.device)
         gb = grads.data_ptr()
         L.call("dgtd_dwconv_bwd_weight", L.ptr(x), L.ptr(du), gb, 1 if has_bias else 0, L.ptr(ws), B, H, W, C, K,
-               L.dtype_code(x), L.stream_ptr(), algo=("hbm", 2 * x.element_size() * x.numel()),
-               key=f"dgtd_dwconv_bwd_weight[k{K},{H}x{W}x{C}]")
+               L.dtype_code(x), L.stream_ptr())
         dw = torch.empty(wshape, dtype=wdtype, device=x.device)
         db = torch.empty(C, dtype=wdtype, device=x.device) if has_bias else None
         L.call("dgtd_dwconv_unpack_grads", gb, L.ptr(dw), L.ptr(db), C, K, L.dtype_code(dw), L.stream_ptr())

@@ -1,7 +1,5 @@
 from __future__ import annotations
 
-import os
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -11,7 +9,6 @@ from . import _native
 
 _WS = {}
 _CODES = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}   # compute dtypes of the C++ Linear nodes
-SPLITK_WGRAD = os.environ.get("DGTD_SPLITK_WGRAD", "1") != "0"   # A/B switch for tools/ and bench runs
 
 
 def _workspace(nbytes: int, device) -> torch.Tensor:
@@ -32,8 +29,7 @@ def colsum(x2d: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.T
         return x2d.sum(0, dtype=torch.float32).to(out_dtype)
     out = torch.empty(C, dtype=out_dtype, device=x2d.device)
     ws = _workspace(L.load().dgtd_colsum_workspace(C), x2d.device)
-    L.call("dgtd_colsum", L.ptr(x2d), L.ptr(out), L.dtype_code(out), L.ptr(ws), rows, C, L.dtype_code(x2d), L.stream_ptr(),
-           algo=("hbm", x2d.element_size() * x2d.numel()), key=f"dgtd_colsum[rows={rows},C={C}]")
+    L.call("dgtd_colsum", L.ptr(x2d), L.ptr(out), L.dtype_code(out), L.ptr(ws), rows, C, L.dtype_code(x2d), L.stream_ptr())
     return out
 
 
@@ -48,8 +44,7 @@ class _ScaleResidualFn(Function):
         g32 = gamma.detach().float().contiguous() if gamma is not None else None
         out = torch.empty_like(x)
         L.call("dgtd_scale_residual_fwd", L.ptr(x), L.ptr(y), L.ptr(s), L.ptr(g32), L.ptr(out), rows, C, rows // B,
-               L.dtype_code(x), L.stream_ptr(), algo=("hbm", 3 * x.element_size() * x.numel()),
-               key=f"dgtd_scale_residual_fwd[rows={rows},C={C}]")
+               L.dtype_code(x), L.stream_ptr())
         ctx.save_for_backward(y, s if s is not None else torch.empty(0, device=x.device),
                               g32 if g32 is not None else torch.empty(0, device=x.device))
         ctx.meta = (s is not None, gamma is not None, gamma.dtype if gamma is not None else None)
@@ -71,8 +66,7 @@ class _ScaleResidualFn(Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if has_g else None
         ws = _workspace(L.load().dgtd_colsum_workspace(C), y.device) if has_g else None
         L.call("dgtd_scale_residual_bwd", L.ptr(g), L.ptr(y), L.ptr(s) if has_s else None, L.ptr(g32) if has_g else None,
-               L.ptr(dy), L.ptr(dgamma), L.ptr(ws), rows, C, rows // B, L.dtype_code(y), L.stream_ptr(),
-               algo=("hbm", (3 if has_g else 2) * y.element_size() * y.numel()), key=f"dgtd_scale_residual_bwd[rows={rows},C={C}]")
+               L.ptr(dy), L.ptr(dgamma), L.ptr(ws), rows, C, rows // B, L.dtype_code(y), L.stream_ptr())
         return g, dy, None, (dgamma.to(gdtype) if has_g else None)
 
 
@@ -94,7 +88,7 @@ def _wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     M >= 32768, 1.8x at M = 8192."""
     M = dy2.shape[0]
     S = min(32, M // 1024)
-    if S < 4 or M % S or dy2.dtype == torch.float32 or not SPLITK_WGRAD:
+    if S < 4 or M % S or dy2.dtype == torch.float32:
         return dy2.t() @ x2
     part = torch.bmm(dy2.view(S, M // S, -1).transpose(1, 2), x2.view(S, M // S, -1))
     return part.sum(0)      # bf16 in, fp32 accumulation inside the reduction, bf16 out: one launch
@@ -141,7 +135,7 @@ class _LinearFn(Function):
 
 def linear(x, w, b=None):
     nat = _native.ops()
-    if nat is not None and x.is_cuda and SPLITK_WGRAD:
+    if nat is not None and x.is_cuda:
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
         if dt in _CODES:
             with torch.autocast("cuda", enabled=False):
@@ -152,7 +146,7 @@ def linear(x, w, b=None):
 def _native_dt(x):
     """(native ops, dtype code) when the C++ nodes can take this call, else (None, None)."""
     nat = _native.ops()
-    if nat is None or not x.is_cuda or not SPLITK_WGRAD:
+    if nat is None or not x.is_cuda:
         return None, None
     dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
     if dt not in _CODES:

@@ -34,8 +34,7 @@ class _PReLUFn(Function):
         x = _dense(x)
         a32 = a.detach().float().contiguous()
         y = torch.empty_like(x)
-        L.call("dgtd_prelu_fwd", L.ptr(x), L.ptr(a32), L.ptr(y), x.numel(), L.dtype_code(x), L.stream_ptr(),
-               algo=("hbm", 2 * x.element_size() * x.numel()), key=f"dgtd_prelu_fwd[n={x.numel()}]")
+        L.call("dgtd_prelu_fwd", L.ptr(x), L.ptr(a32), L.ptr(y), x.numel(), L.dtype_code(x), L.stream_ptr())
         ctx.save_for_backward(x, a32)
         ctx.adtype = a.dtype
         return y
@@ -48,8 +47,7 @@ class _PReLUFn(Function):
             g = torch.empty_like(x).copy_(g)
         dx = torch.empty_like(x)
         da = torch.zeros(1, dtype=torch.float32, device=x.device)
-        L.call("dgtd_prelu_bwd", L.ptr(x), L.ptr(g), L.ptr(a32), L.ptr(dx), L.ptr(da), x.numel(), L.dtype_code(x),
-               L.stream_ptr(), algo=("hbm", 3 * x.element_size() * x.numel()), key=f"dgtd_prelu_bwd[n={x.numel()}]")
+        L.call("dgtd_prelu_bwd", L.ptr(x), L.ptr(g), L.ptr(a32), L.ptr(dx), L.ptr(da), x.numel(), L.dtype_code(x), L.stream_ptr())
         return dx, da.to(ctx.adtype)
 
 
@@ -75,8 +73,7 @@ class _CAGateFn(Function):
         stats = torch.empty(2 * B * C + B * R + 64 * B * C, dtype=torch.float32, device=res.device)
         out = torch.empty_like(res)
         L.call("dgtd_ca_gate_fwd", L.ptr(res), L.ptr(x), L.ptr(w1f), L.ptr(w2f), L.ptr(out), L.ptr(stats), B, H * W, C, R,
-               L.dtype_code(res), L.stream_ptr(), algo=("hbm", 4 * res.element_size() * res.numel()),
-               key=f"dgtd_ca_gate_fwd[B={B},HW={H * W},C={C}]")
+               L.dtype_code(res), L.stream_ptr())
         ctx.save_for_backward(res, w1f, w2f, stats)
         ctx.meta = (w1.shape, w1.dtype, w2.shape, w2.dtype)
         return out
@@ -93,8 +90,7 @@ class _CAGateFn(Function):
         small = torch.empty(2 * R * C + B * C + 64 * B * C + B * 2 * R * C, dtype=torch.float32, device=res.device)
         dw1, dw2, scratch = small[:R * C], small[R * C:2 * R * C], small[2 * R * C:]
         L.call("dgtd_ca_gate_bwd", L.ptr(g), L.ptr(res), L.ptr(w1f), L.ptr(w2f), L.ptr(stats), L.ptr(dres), dw1.data_ptr(),
-               dw2.data_ptr(), scratch.data_ptr(), B, H * W, C, R, L.dtype_code(res), L.stream_ptr(),
-               algo=("hbm", 4 * res.element_size() * res.numel()), key=f"dgtd_ca_gate_bwd[B={B},HW={H * W},C={C}]")
+               dw2.data_ptr(), scratch.data_ptr(), B, H * W, C, R, L.dtype_code(res), L.stream_ptr())
         return dres, g, dw1.view(w1shape).to(w1dtype), dw2.view(w2shape).to(w2dtype)
 
 
@@ -114,8 +110,7 @@ class _BilinearFn(Function):
         x = _nhwc(x)
         B, C, Hi, Wi = x.shape
         y = torch.empty(B, C, Ho, Wo, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        L.call("dgtd_bilinear_fwd", L.ptr(x), L.ptr(y), B, Hi, Wi, Ho, Wo, C, int(align), L.dtype_code(x), L.stream_ptr(),
-               algo=("hbm", x.element_size() * (x.numel() + y.numel())), key=f"dgtd_bilinear_fwd[{Hi}x{Wi}->{Ho}x{Wo},C={C}]")
+        L.call("dgtd_bilinear_fwd", L.ptr(x), L.ptr(y), B, Hi, Wi, Ho, Wo, C, int(align), L.dtype_code(x), L.stream_ptr())
         ctx.meta = (B, C, Hi, Wi, Ho, Wo, align, x.dtype)
         return y
 
@@ -125,8 +120,7 @@ class _BilinearFn(Function):
         B, C, Hi, Wi, Ho, Wo, align, dtype = ctx.meta
         g = _nhwc(g if g.dtype == dtype else g.to(dtype))
         dx = torch.empty(B, C, Hi, Wi, dtype=dtype, device=g.device, memory_format=torch.channels_last)
-        L.call("dgtd_bilinear_bwd", L.ptr(g), L.ptr(dx), B, Hi, Wi, Ho, Wo, C, int(align), L.dtype_code(g), L.stream_ptr(),
-               algo=("hbm", g.element_size() * (g.numel() + dx.numel())), key=f"dgtd_bilinear_bwd[{Hi}x{Wi}<-{Ho}x{Wo},C={C}]")
+        L.call("dgtd_bilinear_bwd", L.ptr(g), L.ptr(dx), B, Hi, Wi, Ho, Wo, C, int(align), L.dtype_code(g), L.stream_ptr())
         return dx, None, None, None
 
 
@@ -230,7 +224,7 @@ def cab(x: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor, a: torch.Tensor, cw
     """The whole CAB (cod.py:436-451) - conv3x3 -> PReLU -> conv3x3 -> channel-attention gate -> + x - as ONE autograd node of the C++
     binding layer (csrc_torch/bindings.cpp CabFn): the PReLU and its backward ride in the convolutions' epilogues
     (dgtd_conv3x3_fwd_ex), the skip gradient is added inside the first convolution's input-gradient launch.  None when the node is not
-    available (Python bindings, profiler attached): the caller composes the separate ops."""
+    available (Python bindings): the caller composes the separate ops."""
     nat = _native.ops()
     if nat is None or not x.is_cuda or not hasattr(nat, "cab"):
         return None
@@ -249,7 +243,7 @@ class _SamFn(Function):
         stats = torch.empty(L.load().dgtd_sam_stats_floats(B, C, R), dtype=torch.float32, device=xh.device)
         out = torch.empty_like(xh)
         L.call("dgtd_sam_fwd", L.ptr(xh), L.ptr(xl), *(L.ptr(w) for w in ws), L.ptr(out), L.ptr(stats), B, H * W, C, R, L.dtype_code(xh),
-               L.stream_ptr(), algo=("hbm", 5 * xh.element_size() * xh.numel()), key=f"dgtd_sam_fwd[B={B},HW={H * W},C={C}]")
+               L.stream_ptr())
         ctx.save_for_backward(xh, xl, *ws, stats)
         ctx.meta = [(w.shape, w.dtype) for w in (w1, w2, v1, v2)]
         return out
@@ -265,8 +259,7 @@ class _SamFn(Function):
         dw = torch.empty(3 * R * C + R, dtype=torch.float32, device=xh.device)
         scratch = torch.empty(L.load().dgtd_sam_scratch_floats(B, C), dtype=torch.float32, device=xh.device)
         L.call("dgtd_sam_bwd", L.ptr(g), L.ptr(xh), L.ptr(xl), L.ptr(w1f), L.ptr(w2f), L.ptr(v1f), L.ptr(v2f), L.ptr(stats), L.ptr(dxh), L.ptr(dxl),
-               L.ptr(dw), L.ptr(scratch), B, H * W, C, R, L.dtype_code(xh), L.stream_ptr(),
-               algo=("hbm", 7 * xh.element_size() * xh.numel()), key=f"dgtd_sam_bwd[B={B},HW={H * W},C={C}]")
+               L.ptr(dw), L.ptr(scratch), B, H * W, C, R, L.dtype_code(xh), L.stream_ptr())
         parts = (dw[:R * C], dw[R * C:2 * R * C], dw[2 * R * C:3 * R * C], dw[3 * R * C:])
         return (dxh, dxl) + tuple(p.view(shape).to(dtype) for p, (shape, dtype) in zip(parts, ctx.meta))
 
@@ -297,9 +290,7 @@ class _BatchNormFn(Function):
         save = torch.empty(2 * C, dtype=torch.float32, device=x.device)
         scratch = torch.empty(L.load().dgtd_batchnorm_scratch(C), dtype=torch.float32, device=x.device)
         L.call("dgtd_batchnorm_fwd", L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(running_mean), L.ptr(running_var), L.ptr(num_batches), L.ptr(y),
-               L.ptr(save), L.ptr(scratch), N, C, float(eps), float(momentum), int(training), L.dtype_code(x), L.stream_ptr(),
-               algo=("hbm", (3 if training else 2) * x.element_size() * x.numel()),
-               key=f"dgtd_batchnorm_fwd[{'train' if training else 'eval'},N={N},C={C}]")
+               L.ptr(save), L.ptr(scratch), N, C, float(eps), float(momentum), int(training), L.dtype_code(x), L.stream_ptr())
         ctx.save_for_backward(x, gamma, save)
         ctx.training = bool(training)
         return y
@@ -317,7 +308,7 @@ class _BatchNormFn(Function):
         d = torch.empty(2 * C, dtype=torch.float32, device=x.device)
         scratch = torch.empty(L.load().dgtd_batchnorm_scratch(C), dtype=torch.float32, device=x.device)
         L.call("dgtd_batchnorm_bwd", L.ptr(g), L.ptr(x), L.ptr(gamma), L.ptr(save), L.ptr(dx), d[:C].data_ptr(), d[C:].data_ptr(), L.ptr(scratch),
-               N, C, L.dtype_code(x), L.stream_ptr(), algo=("hbm", 5 * x.element_size() * x.numel()), key=f"dgtd_batchnorm_bwd[N={N},C={C}]")
+               N, C, L.dtype_code(x), L.stream_ptr())
         return dx, d[:C], d[C:], None, None, None, None, None, None
 
 

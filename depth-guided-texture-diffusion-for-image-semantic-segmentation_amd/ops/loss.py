@@ -30,8 +30,7 @@ class _SegLossFn(Function):
         assert K == 5 and label.numel() == B * S * S and lo.dtype == torch.float32 and label.dtype == torch.float32
         ws = torch.empty(L.load().dgtd_seg_loss_workspace(B, S), dtype=torch.uint8, device=lo.device)
         loss = torch.empty(1, dtype=torch.float32, device=lo.device)
-        L.call("dgtd_seg_loss_fwd", L.ptr(lo), L.ptr(label), L.ptr(mix), L.ptr(loss), L.ptr(ws), B, S, hs, L.stream_ptr(),
-               algo=("hbm", 4.0 * B * S * S * 4), key=f"dgtd_seg_loss_fwd[B={B},S={S}]")
+        L.call("dgtd_seg_loss_fwd", L.ptr(lo), L.ptr(label), L.ptr(mix), L.ptr(loss), L.ptr(ws), B, S, hs, L.stream_ptr())
         ctx.save_for_backward(lo, label, mix, ws)
         return loss[0]
 
@@ -43,8 +42,7 @@ class _SegLossFn(Function):
         S = label.shape[-1]
         g = g.reshape(1).float().contiguous()
         dlo = torch.empty_like(lo)
-        L.call("dgtd_seg_loss_bwd", L.ptr(lo), L.ptr(label), L.ptr(mix), L.ptr(g), L.ptr(dlo), L.ptr(ws), B, S, hs, L.stream_ptr(),
-               algo=("hbm", 4.0 * B * S * S * 2 * 4), key=f"dgtd_seg_loss_bwd[B={B},S={S}]")
+        L.call("dgtd_seg_loss_bwd", L.ptr(lo), L.ptr(label), L.ptr(mix), L.ptr(g), L.ptr(dlo), L.ptr(ws), B, S, hs, L.stream_ptr())
         return dlo, None, None
 
 

@@ -32,8 +32,7 @@ def ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
         raise L.DgtdError("ms_deform_attn: value, sampling_locations and attention_weights must share one dtype")
     out = torch.empty(N, Lq, M * D, dtype=value.dtype, device=value.device)
     L.call("dgtd_ms_deform_attn_fwd", L.ptr(value), L.ptr(shapes), L.ptr(lsi), L.ptr(sampling_locations), L.ptr(attention_weights),
-           L.ptr(out), N, S, M, D, Lv, Lq, P, _code(value), L.stream_ptr(),
-           algo=("hbm", value.element_size() * (out.numel() * (4 * Lv * P + 1))), key=f"dgtd_ms_deform_attn_fwd[N={N},Lq={Lq},M={M},D={D},L={Lv},P={P}]")
+           L.ptr(out), N, S, M, D, Lv, Lq, P, _code(value), L.stream_ptr())
     return out
 
 
@@ -51,8 +50,7 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
     gv = torch.zeros_like(value)
     gl, ga = torch.empty_like(loc), torch.empty_like(attn)
     L.call("dgtd_ms_deform_attn_bwd", L.ptr(value), L.ptr(shapes), L.ptr(lsi), L.ptr(loc), L.ptr(attn), L.ptr(go), L.ptr(gv), L.ptr(gl),
-           L.ptr(ga), N, S, M, D, Lv, Lq, P, _code(value), L.stream_ptr(),
-           algo=("hbm", value.element_size() * (go.numel() * (8 * Lv * P + 1))), key=f"dgtd_ms_deform_attn_bwd[N={N},Lq={Lq},M={M},D={D},L={Lv},P={P}]")
+           L.ptr(ga), N, S, M, D, Lv, Lq, P, _code(value), L.stream_ptr())
     return [gv, gl, ga]
 
 

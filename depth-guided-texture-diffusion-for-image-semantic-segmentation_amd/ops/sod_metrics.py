@@ -44,8 +44,7 @@ def sod_metrics_rows(pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
     B, H, W = pred.shape
     out = torch.empty(B, ROW, dtype=torch.float64, device=pred.device)
     ws = torch.empty(L.load().dgtd_sod_metrics_workspace(B), dtype=torch.uint8, device=pred.device)
-    L.call("dgtd_sod_metrics", L.ptr(pred), L.dtype_code(pred), L.ptr(gt), L.ptr(out), L.ptr(ws), B, H, W, L.stream_ptr(),
-           algo=("hbm", B * H * W * (2.0 * pred.element_size() + 8.0)), key=f"dgtd_sod_metrics[B={B},{H}x{W}]")
+    L.call("dgtd_sod_metrics", L.ptr(pred), L.dtype_code(pred), L.ptr(gt), L.ptr(out), L.ptr(ws), B, H, W, L.stream_ptr())
     return out
 
 

@@ -25,8 +25,7 @@ def edt_nearest(mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     B, H, W = m.shape
     dist2 = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
     index = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
-    L.call("dgtd_edt_nearest", L.ptr(m), L.ptr(dist2), L.ptr(index), B, H, W, L.stream_ptr(),
-           algo=("hbm", B * H * W * 17.0), key=f"dgtd_edt_nearest[B={B},{H}x{W}]")
+    L.call("dgtd_edt_nearest", L.ptr(m), L.ptr(dist2), L.ptr(index), B, H, W, L.stream_ptr())
     return dist2.reshape(mask.shape), index.reshape(mask.shape)
 
 
@@ -38,8 +37,7 @@ def weighted_fmeasure_rows(pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor
     B, H, W = pred.shape
     out = torch.empty(B, dtype=torch.float64, device=pred.device)
     ws = torch.empty(L.load().dgtd_wfm_workspace(B, H, W), dtype=torch.uint8, device=pred.device)
-    L.call("dgtd_wfm", L.ptr(pred), L.dtype_code(pred), L.ptr(gt), L.ptr(out), L.ptr(ws), B, H, W, L.stream_ptr(),
-           algo=("hbm", B * H * W * (pred.element_size() + 33.0)), key=f"dgtd_wfm[B={B},{H}x{W}]")
+    L.call("dgtd_wfm", L.ptr(pred), L.dtype_code(pred), L.ptr(gt), L.ptr(out), L.ptr(ws), B, H, W, L.stream_ptr())
     return out
 
 

@@ -95,3 +95,21 @@ def test_block_run_is_a_no_op_without_the_native_layer():
     assert "_dgtd_arena_token" not in owner.__dict__
     ops.NO_RUN.at(0)
     ops.NO_RUN.roles(out=1)
+
+
+def test_single_path_blocks_on_cpu_tensors():
+    """Block and convnext_Block have one composition, the fused one, and it runs on the HIP device only: a CPU tensor raises DgtdError
+    (there is no second, unfused branch to fall into).  CAB keeps its literal path for tensors outside the device gates."""
+    import dgtd
+    from dgtd._lib import DgtdError
+    with pytest.raises(DgtdError):
+        dgtd.nn.Block(64, 1)(torch.randn(1, 4, 64), 2, 2)
+    with pytest.raises(DgtdError):
+        dgtd.nn.convnext_Block(128).forward_nhwc(torch.randn(1, 2, 2, 128))
+    x = torch.randn(1, 32, 4, 4)
+    cab = dgtd.nn.CAB(32, 3, 4, False, torch.nn.PReLU())
+    with torch.no_grad():
+        y = cab(x)
+        want = cab.CA(cab.body(x)) + x
+    assert y.shape == x.shape
+    torch.testing.assert_close(y, want, rtol=0, atol=0)

@@ -1069,7 +1069,6 @@ def test_conv3x3_fwd_ex_epilogues(dgtd, C, S, half):
 def test_cab_node_vs_composition_and_fp32(dgtd, C, S, red, half):
     """The CAB as ONE C++ node (ops.cab) against the composition of the separate ops it replaces and against fp32 torch: output and the
     gradients of the input, both convolution weights, the shared PReLU slope and the two channel-attention weights."""
-    M = dgtd.nn.modules
     act = torch.nn.PReLU()
     cab = dgtd.nn.CAB(C, 3, red, bias=False, act=act).cuda()
     with torch.no_grad():
@@ -1080,20 +1079,15 @@ def test_cab_node_vs_composition_and_fp32(dgtd, C, S, red, half):
     g = _rand(2, C, S, S, seed=2).to(half).contiguous(memory_format=torch.channels_last)
     params = [cab.body[0].weight, cab.body[2].weight, act.weight, cab.CA.conv_du[0].weight, cab.CA.conv_du[2].weight]
 
-    def run(node):
-        old = M._USE["cab_node"]
-        M._USE["cab_node"] = node
-        try:
-            xs = x.clone().requires_grad_()
-            with torch.autocast("cuda", dtype=half):
-                y = cab(xs)
-            grads = torch.autograd.grad(y, [xs] + params, g)
-        finally:
-            M._USE["cab_node"] = old
+    def run(fn):
+        xs = x.clone().requires_grad_()
+        with torch.autocast("cuda", dtype=half):
+            y = fn(xs)
+        grads = torch.autograd.grad(y, [xs] + params, g)
         return y.detach().float(), [t.float() for t in grads]
 
-    y1, g1 = run(True)
-    y0, g0 = run(False)
+    y1, g1 = run(cab)
+    y0, g0 = run(cab.composition)
     torch.testing.assert_close(y1, y0, atol=2e-2, rtol=2e-2)
     names = ["dx", "dw0", "dw1", "da", "dcw1", "dcw2"]
     for n, a, b_ in zip(names, g1, g0):
