@@ -71,6 +71,12 @@ SIGNATURES = {
     "dgtd_diffuse_tail_fwd": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _vp]),
     "dgtd_diffuse_tail_bwd_workspace": (_i64, [_i]),
     "dgtd_diffuse_tail_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _vp]),
+    "dgtd_diffuser_cfg_workspace": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "dgtd_diffuser_cfg_fwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dgtd_diffuser_cfg_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dgtd_diffuse_tail_cfg_fwd": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "dgtd_diffuse_tail_cfg_bwd_workspace": (_i64, [_i, _i]),
+    "dgtd_diffuse_tail_cfg_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _i, _i, _vp]),
     "dgtd_adamw_flat": (_i, [_fp, _fp, _fp, _fp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "dgtd_adamw_flat_amp": (_i, [_fp, _fp, _fp, _fp, _vp, _i, _i64, _f, _f, _f, _f, _f, _f, _f, _fp, _fp, _vp]),
     "dgtd_adamw_flat_g16": (_i, [_fp, _vp, _fp, _fp, _vp, _i, _i64, _f, _f, _f, _f, _f, _f, _f, _fp, _fp, _vp]),

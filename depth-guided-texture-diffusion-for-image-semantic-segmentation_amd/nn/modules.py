@@ -346,10 +346,10 @@ class ShapePropEncoder(nn.Module):
 class ShapePropWeightRegressor(nn.Module):
     """cod.py:1051-1060."""
 
-    def __init__(self, in_channels, latent_dim):
+    def __init__(self, in_channels, latent_dim, k=7):
         super().__init__()
-        self.latent_dim = latent_dim
-        self.reg = Conv2d(in_channels, latent_dim * 49, kernel_size=1)
+        self.latent_dim, self.k = latent_dim, k
+        self.reg = Conv2d(in_channels, latent_dim * k * k, kernel_size=1)
 
     def forward(self, x):
         return torch.sigmoid(self.reg(x))
@@ -385,17 +385,34 @@ def fft_highpass(x: torch.Tensor, rate: float) -> torch.Tensor:
     return torch.fft.ifft2(torch.fft.ifftshift(f, dim=(-2, -1)), norm="forward").real.abs()
 
 
-class prompt_encoder(nn.Module):
-    """cod.py:1228-1306."""
+DIFFUSER_KEYS = {"grid": "grid", "k": "k", "max_step": "max_step", "latent_dim": "diffuser_latent"}
 
-    def __init__(self, latent_dim, embed_dim, depth, fusion=False):
+
+def diffuser_kwargs(diffuser: Optional[dict]) -> dict:
+    """The ``diffuser`` option of ``cod`` / ``Hitnet`` / the PVT backbones -> ``prompt_encoder`` keyword arguments.  Keys: ``grid`` (12),
+    ``k`` (7), ``max_step`` (4; negative = ``grid`` steps), ``latent_dim`` (24); anything else is a TypeError, like a misspelt keyword."""
+    diffuser = dict(diffuser or {})
+    unknown = sorted(set(diffuser) - set(DIFFUSER_KEYS))
+    if unknown:
+        raise TypeError(f"diffuser got unexpected key(s) {unknown}; known: {sorted(DIFFUSER_KEYS)}")
+    return {DIFFUSER_KEYS[key]: int(v) for key, v in diffuser.items()}
+
+
+class prompt_encoder(nn.Module):
+    """cod.py:1228-1306.  ``grid`` (cod.py:1283), ``k`` / ``max_step`` (cod.py:1181) and ``diffuser_latent`` are the texture diffuser's
+    hyper-parameters; ``diffuser_latent`` (default: ``latent_dim``) sizes the regressor, ``encoder1`` and ``message_passing.conv`` only -
+    ``encoder2`` keeps emitting the 24 channels the prompt decoders are built for."""
+
+    def __init__(self, latent_dim, embed_dim, depth, fusion=False, grid=12, k=7, max_step=4, diffuser_latent=None):
         super().__init__()
         self.embed_dim, self.depth = embed_dim, depth
-        self.propagation_weight_regressor = ShapePropWeightRegressor(3, latent_dim)
-        self.encoder1 = Conv2d(1, latent_dim, 1)
+        self.grid = grid
+        dl = latent_dim if diffuser_latent is None else diffuser_latent
+        self.propagation_weight_regressor = ShapePropWeightRegressor(3, dl, k)
+        self.encoder1 = Conv2d(1, dl, 1)
         self.encoder2 = ShapePropEncoder(3, 24)
         self.adaptor = Conv2d(6, 3, 1)  # constructed, never called (cod.py:1251)
-        self.message_passing = MessagePassing(latent_dim, img_size=384, sym_norm=False)
+        self.message_passing = MessagePassing(dl, img_size=384, k=k, max_step=max_step, sym_norm=False)
         self.freq_nums = 0.3
 
     def fft(self, x, rate):
@@ -405,12 +422,12 @@ class prompt_encoder(nn.Module):
         with torch.autocast("cuda", enabled=False):
             image32 = image.float()
             x = self.fft(image32, self.freq_nums) if x_hp is None else x_hp
-            # one fused launch per (image, latent channel): regressor + depth embedding + 4 propagation steps
+            # one fused launch per (image, latent channel): regressor + depth embedding + the propagation steps
             reg = self.propagation_weight_regressor.reg
-            x4 = ops.diffuser_state(x, cues, *wb(reg), *wb(self.encoder1))
-            # 1x1 conv 24->3, bilinear 12 -> S (the reference pins 384, cod.py:1252), + image: one HBM-bound pass
-            mp = self.message_passing.conv
-            fused = ops.diffuse_tail(x4, *wb(mp), image32)
+            mp = self.message_passing
+            x4 = ops.diffuser_state(x, cues, *wb(reg), *wb(self.encoder1), grid=self.grid, k=mp.k, steps=mp.max_step)
+            # 1x1 conv latent->3, bilinear grid -> S (the reference pins 384, cod.py:1252), + image: one HBM-bound pass
+            fused = ops.diffuse_tail(x4, *wb(mp.conv), image32)
         return x, self.encoder2(fused)
 
 
@@ -507,7 +524,8 @@ class PyramidVisionTransformerImpr(nn.Module):
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512],
                  num_heads=[1, 2, 4, 8], mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0.,
-                 attn_drop_rate=0., drop_path_rate=0., norm_layer=None, depths=[3, 4, 6, 3], sr_ratios=[8, 4, 2, 1]):
+                 attn_drop_rate=0., drop_path_rate=0., norm_layer=None, depths=[3, 4, 6, 3], sr_ratios=[8, 4, 2, 1],
+                 diffuser: Optional[dict] = None):
         super().__init__()
         self.num_classes, self.depths = num_classes, depths
         chans = [in_chans] + list(embed_dims[:3])
@@ -524,7 +542,7 @@ class PyramidVisionTransformerImpr(nn.Module):
             setattr(self, f"norm{i + 1}", LayerNorm(embed_dims[i], eps=1e-6))
             cur += depths[i]
         self.latent_dim = LATENT
-        self.prompt_encoder = prompt_encoder(self.latent_dim, embed_dims, depths, True)
+        self.prompt_encoder = prompt_encoder(self.latent_dim, embed_dims, depths, True, **diffuser_kwargs(diffuser))
         self.prompt_decoder = nn.Sequential(*[prompt_decoder(self.latent_dim, embed_dims[i], depths[i], True) for i in range(4)])
         self.apply(_init_weights)
         self.batch = 0
@@ -575,7 +593,8 @@ def _pvt_variant(name, depths, mlp_ratios, doc):
     def __init__(self, **kwargs):
         PyramidVisionTransformerImpr.__init__(self, patch_size=4, embed_dims=[64, 128, 320, 512], num_heads=[1, 2, 5, 8],
                                               mlp_ratios=mlp_ratios, qkv_bias=True, depths=depths, sr_ratios=[8, 4, 2, 1],
-                                              drop_rate=0.0, drop_path_rate=kwargs.get("drop_path_rate", 0.1))
+                                              drop_rate=0.0, drop_path_rate=kwargs.get("drop_path_rate", 0.1),
+                                              diffuser=kwargs.get("diffuser"))
     return type(name, (PyramidVisionTransformerImpr,), {"__init__": __init__, "__doc__": doc})
 
 
@@ -719,11 +738,11 @@ class Hitnet(nn.Module):
     """cod.py:685-807."""
 
     def __init__(self, channel=32, n_feat=32, scale_unetfeats=32, kernel_size=3, reduction=4, bias=False, act=None,
-                 drop_path_rate=0.1, backbone: str = "pvt_v2_b2"):
+                 drop_path_rate=0.1, backbone: str = "pvt_v2_b2", diffuser: Optional[dict] = None):
         super().__init__()
         act = act if act is not None else nn.PReLU()  # ONE shared instance (default argument at cod.py:686)
         # the reference hard-codes pvt_v2_b2 (cod.py:689); b1/b3/b4/b5 fit the same 64/128/320/512 Translayers ("tier B", SURVEY §7)
-        self.backbone = PVT_VARIANTS[backbone](drop_path_rate=drop_path_rate)
+        self.backbone = PVT_VARIANTS[backbone](drop_path_rate=drop_path_rate, diffuser=diffuser)
         if drop_path_rate == 0.0:
             for m in self.backbone.modules():
                 if isinstance(m, DropPath):
@@ -812,13 +831,18 @@ class cod(nn.Module):
     ``compute_dtype``: torch.float32 = exact-fp32 kernels (parity mode); torch.bfloat16 = bf16 MFMA
     kernels + library GEMM/conv under bf16 autocast with fp32 master weights (throughput mode); torch.float16 = the same
     with IEEE half (fp16 MFMA) - the reference's own AMP recipe (AmpOptimWrapper, config/sod.yml:57): pair it with
-    ``runner.LossScaler`` + ``runner.FlatAdamW(scaler=...)``."""
+    ``runner.LossScaler`` + ``runner.FlatAdamW(scaler=...)``.
+    ``diffuser``: the texture diffuser's hyper-parameters, any of ``{"grid": 12, "k": 7, "max_step": 4, "latent_dim": 24}`` (``diffuser_kwargs``).
+    State-dict keys do not depend on it; the regressor, ``encoder1`` and ``message_passing.conv`` change shape, so a checkpoint of
+    another configuration fails to load with torch's size-mismatch error."""
 
     def __init__(self, win_size=None, filter_ratio=None, using_depth=None, using_sam=None, finetune=None,
                  binary_thresh=None, pretrain_sam=None, head=None, img_size: int = 384,
-                 compute_dtype: torch.dtype = torch.float32, drop_path_rate: float = 0.1, backbone: str = "pvt_v2_b2"):
+                 compute_dtype: torch.dtype = torch.float32, drop_path_rate: float = 0.1, backbone: str = "pvt_v2_b2",
+                 diffuser: Optional[dict] = None):
         super().__init__()
-        self.hitnet = Hitnet(drop_path_rate=drop_path_rate, backbone=backbone)
+        diffuser_kwargs(diffuser)                    # a misspelt key fails here, before anything is built
+        self.hitnet = Hitnet(drop_path_rate=drop_path_rate, backbone=backbone, diffuser=diffuser)
         self.batch = 0
         self.compute_dtype = compute_dtype
         self._dp_plan = {"masks": None}

@@ -4,7 +4,9 @@ ignores, cod.py:38-46), ``optim_wrapper`` (AdamW, ``paramwise_cfg.custom_keys`` 
 ``param_scheduler`` (CosineAnnealingLR by epoch), ``default_hooks.logger.interval`` / ``checkpoint.interval``,
 ``custom_hooks: our_init``, ``*_dataloader.sampler`` (DefaultSampler), ``val_evaluator``, ``optim_wrapper.type: AmpOptimWrapper``
 (= fp16 autocast + dynamic loss scaling when the runner is built with ``compute_dtype=torch.float16``).  The external nest/mmengine runner is out of scope; this is what drives the HIP-backed model from
-the same file.  Datasets need real data, so the loop is fed by any iterable of the dataset dict contract (runner/data.py)."""
+the same file.  ``model:`` keys beyond ``type`` reach the model class as keyword arguments (``build_model``), so
+``model: {type: cod, diffuser: {grid: 22, k: 5, max_step: 6}}`` selects a texture-diffuser configuration (keys ``grid``, ``k``, ``max_step``,
+``latent_dim``; an unknown key is a TypeError) with no further runner code.  Datasets need real data, so the loop is fed by any iterable of the dataset dict contract (runner/data.py)."""
 from __future__ import annotations
 
 import math

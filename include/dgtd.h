@@ -255,6 +255,30 @@ int64_t dgtd_diffuse_tail_bwd_workspace(int B);
 int dgtd_diffuse_tail_bwd(const float* gout, const float* x4, const float* cw, float* g4, float* d_cw,
                           float* d_cb, void* workspace, int B, int S, dgtd_stream s);
 
+/* ---- Texture diffuser front end, configurable (fp32) ------------------------------------------
+ * The same computation with the four hyper-parameters at run time: grid 2 <= G <= 64, neighbourhood K odd in 3..11 (zero padding K/2),
+ * 0 <= steps <= 64 propagation steps, latent width 1 <= LAT <= 64; S a positive multiple of 4, B > 0.  Anything else: status 2, nothing
+ * launched.  reg_w [LAT*K*K,3], reg_b [LAT*K*K] (regressor channel = c*K*K + ky*K + kx); enc_w [LAT], enc_b [LAT] -> x4 [B,LAT,G,G].
+ * The entries above stay the path of (12, 7, 4, 24).  The normalised weights (and, backward, the per-step states and gradients) live
+ * in `workspace`: dgtd_diffuser_cfg_workspace(..., backward) bytes (-1 outside the domain), contents undefined before and after.
+ * No allocation, no host synchronisation: capturable.  The forward has no atomics (bit-reproducible).                              */
+int64_t dgtd_diffuser_cfg_workspace(int B, int S, int G, int K, int steps, int LAT, int backward);
+int dgtd_diffuser_cfg_fwd(const float* x_hp, const float* depth, const float* reg_w, const float* reg_b,
+                          const float* enc_w, const float* enc_b, float* x4, void* workspace, int B, int S,
+                          int G, int K, int steps, int LAT, dgtd_stream s);
+/* d_* ZEROED by the caller (atomics over batch); with steps == 0 d_reg_w / d_reg_b are not touched (exact zeros). */
+int dgtd_diffuser_cfg_bwd(const float* x_hp, const float* depth, const float* reg_w, const float* reg_b,
+                          const float* enc_w, const float* enc_b, const float* g4, float* d_reg_w,
+                          float* d_reg_b, float* d_enc_w, float* d_enc_b, void* workspace, int B, int S,
+                          int G, int K, int steps, int LAT, dgtd_stream s);
+/* out [B,3,S,S] = bilinear_{G->S, align_corners=False}(conv1x1(x4 [B,LAT,G,G]; cw [3,LAT], cb [3])) + image; G > S allowed. */
+int dgtd_diffuse_tail_cfg_fwd(const float* x4, const float* cw, const float* cb, const float* image,
+                              float* out, int B, int S, int G, int LAT, dgtd_stream s);
+int64_t dgtd_diffuse_tail_cfg_bwd_workspace(int B, int G);
+/* g4 [B,LAT,G,G] overwritten; d_cw [3,LAT], d_cb [3] ZEROED by the caller.                          */
+int dgtd_diffuse_tail_cfg_bwd(const float* gout, const float* x4, const float* cw, float* g4, float* d_cw,
+                              float* d_cb, void* workspace, int B, int S, int G, int LAT, dgtd_stream s);
+
 /* ---- Hitnet CAB decoder glue on channels_last maps viewed as [B, HW, C] ------------------------------
  * PReLU with ONE shared slope a[1] (the default-argument nn.PReLU() of twig/model/cod.py:686, applied at cod.py:444-446):
  * y = x > 0 ? x : a*x over n elements (any dense layout).                                                             */
