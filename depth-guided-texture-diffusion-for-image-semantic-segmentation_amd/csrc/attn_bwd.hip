@@ -528,6 +528,7 @@ extern "C" int dgtd_sra_attn_bwd(const void* q, const void* kv, const void* out,
   DGTD_PROF(s, DGTD_MFMA, 10.0 * B * heads * (double)N * Nkv * 64, "dgtd_sra_attn_bwd[B=%d,N=%d,Nkv=%d,h=%d]", B, N, Nkv, heads);
   DGTD_REQUIRE(B > 0 && N > 0 && Nkv > 0 && heads > 0, "sra_attn_bwd: bad sizes B=%d N=%d Nkv=%d heads=%d", B, N, Nkv, heads);
   DGTD_REQUIRE(dt == DGTD_F32 || DGTD_IS_HALF(dt), "sra_attn_bwd: bad dtype %d", (int)dt);
+  DGTD_REQUIRE(std::isfinite(scale) && scale > 0.f, "sra_attn_bwd: scale must be finite and > 0, got %g", (double)scale);
   hipStream_t st = (hipStream_t)s;
   float* delta = (float*)workspace;
   const int64_t items = (int64_t)B * N * heads;

@@ -317,6 +317,8 @@ extern "C" int dgtd_sra_attn_fwd(const void* q, const void* kv, void* out, float
   DGTD_PROF(s, DGTD_MFMA, 4.0 * B * heads * (double)N * Nkv * 64, "dgtd_sra_attn_fwd[B=%d,N=%d,Nkv=%d,h=%d]", B, N, Nkv, heads);
   DGTD_REQUIRE(B > 0 && N > 0 && Nkv > 0 && heads > 0, "sra_attn_fwd: bad sizes B=%d N=%d Nkv=%d heads=%d", B, N, Nkv, heads);
   DGTD_REQUIRE(heads <= 65535 && B <= 65535, "sra_attn_fwd: grid limits");
+  // the 16-bit kernel takes the row maximum BEFORE scaling (it commutes with a positive scale only); the fp32 kernel scales first
+  DGTD_REQUIRE(std::isfinite(scale) && scale > 0.f, "sra_attn_fwd: scale must be finite and > 0, got %g", (double)scale);
   const int qtw = pick_qtw(N, B * heads);
   dim3 grid((unsigned)cdiv(N, 128 * qtw), heads, B), block(256);
   const float sl2 = scale * LOG2E;

@@ -44,6 +44,9 @@ class _SraAttnFn(Function):
 
 
 def sra_attention(q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
+    scale = float(scale)
+    if not (0.0 < scale < float("inf")):       # NaN fails both comparisons; the C entries refuse it too (include/dgtd.h)
+        raise L.DgtdError(f"sra_attention: scale must be finite and > 0, got {scale}")
     nat = _native.ops()
     if nat is not None and q.is_cuda:
         return nat.sra_attention(q, kv, heads, float(scale))

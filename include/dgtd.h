@@ -71,11 +71,14 @@ int dgtd_layernorm_bwd_partial(const void* dy, const void* x, const float* gamma
  * q   [B, N,   heads*64]      = output of Attention.q   (cod.py:902) — head h in cols [64h, 64h+64)
  * kv  [B, Nkv, 2*heads*64]    = output of Attention.kv  (cod.py:908) — K then V, same head split
  * out [B, N,   heads*64]      = (attn @ v).transpose(1,2).reshape(B,N,C) (cod.py:917)
- * lse [B, heads, N] fp32      = log-sum-exp of the scaled scores (saved for the backward)       */
+ * lse [B, heads, N] fp32      = log-sum-exp of the scaled scores (saved for the backward)
+ * scale must be finite and > 0 (forward and backward refuse anything else before any launch): the 16-bit forward takes the row maximum
+ * of the raw scores, which commutes with a positive scale only.                                  */
 int dgtd_sra_attn_fwd(const void* q, const void* kv, void* out, float* lse,
                       int B, int N, int Nkv, int heads, float scale, dgtd_dtype dt, dgtd_stream s);
-/* dq [B,N,C] (dt);  dkv_f32 [B,Nkv,2C] fp32.  DGTD_F32: must be ZEROED by the caller (atomically accumulated).  DGTD_BF16 / DGTD_F16:
- * every element is overwritten (the query chunks of the key-stationary dK/dV kernel write plain partial slabs into the workspace and
+/* dq [B,N,C] (dt): every element is overwritten.  dkv_f32 [B,Nkv,2C] fp32, the contract differs by dt:
+ *   DGTD_F32: must be ZEROED by the caller (atomically accumulated; summation order, hence the last bits, vary between launches).
+ *   DGTD_BF16 / DGTD_F16: every element is overwritten (the query chunks of the key-stationary dK/dV kernel write plain partial slabs into the workspace and
  * one reduce launch sums them; no atomics), so the result is bit-reproducible and the buffer needs no initialisation.
  * workspace: dgtd_sra_attn_bwd_workspace(B,N,heads) bytes = delta = rowsum(dO*O) (computed inside the dQ kernel) + 64 MB of slabs.   */
 int64_t dgtd_sra_attn_bwd_workspace(int B, int N, int heads);

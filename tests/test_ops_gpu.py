@@ -68,10 +68,12 @@ def _attn_ref(q, kv, heads, scale):
 
 
 # (B, N, Nkv, heads): the four PVT stages at S=256 and S=512, S=384's N_kv=144, ragged/tiny cases,
-# and N_kv=1024 (S=1024) which exercises the multi-chunk online softmax and the key-slice loop of the backward.
+# and N_kv=1024 (S=1024) which exercises the multi-chunk online softmax and the key-slice loop of the backward; the last two put both
+# binding layers on the qtw > 1 launch (staged K/V reused across query tiles) and on partial dK/dV slabs with a short second chunk.
 ATTN_SHAPES = [(2, 4096, 64, 1), (2, 1024, 64, 2), (2, 256, 64, 5), (2, 64, 64, 8),
                (1, 16384, 256, 1), (1, 4096, 256, 2), (2, 1024, 256, 5), (2, 256, 256, 8),
-               (1, 2304, 144, 2), (2, 4, 4, 8), (1, 1, 1, 8), (3, 100, 37, 2), (1, 2048, 1024, 2)]
+               (1, 2304, 144, 2), (2, 4, 4, 8), (1, 1, 1, 8), (3, 100, 37, 2), (1, 2048, 1024, 2),
+               (16, 1000, 37, 8), (8, 200, 200, 8)]
 
 
 @pytest.mark.parametrize("shape", ATTN_SHAPES, ids=[str(s) for s in ATTN_SHAPES])
@@ -99,6 +101,17 @@ def test_sra_attention_fwd_bwd(dgtd, shape, dtype):
         torch.testing.assert_close(hq.float(), gq, atol=5e-2, rtol=5e-2)
         rel = (hkv.float() - gkv).norm() / gkv.norm()
         assert rel < 2e-2, rel
+
+
+@pytest.mark.parametrize("scale", [0.0, -0.125, float("nan")])
+def test_sra_attention_refuses_non_positive_scale(dgtd, scale):
+    """the 16-bit forward takes the row maximum before scaling, the fp32 one scales first: a scale that is not finite and > 0 would give
+    different arithmetic per dtype, so both binding layers refuse it (the C entries do too: test_attn_numerics_gpu.py)"""
+    q, kv = _rand(1, 32, 64, seed=1), _rand(1, 32, 128, seed=2)
+    with pytest.raises(dgtd._lib.DgtdError, match="scale"):
+        dgtd.ops.sra_attention(q, kv, 1, scale)
+    out = dgtd.ops.sra_attention(q, kv, 1, 0.125)              # the library stays usable
+    torch.testing.assert_close(out, _attn_ref(q, kv, 1, 0.125), atol=2e-5, rtol=2e-5)
 
 
 def test_attention_spiked_scores_online_softmax(dgtd):
