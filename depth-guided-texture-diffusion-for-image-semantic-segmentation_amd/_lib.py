@@ -81,6 +81,10 @@ SIGNATURES = {
     "dgtd_adamw_flat_amp": (_i, [_fp, _fp, _fp, _fp, _vp, _i, _i64, _f, _f, _f, _f, _f, _f, _f, _fp, _fp, _vp]),
     "dgtd_adamw_flat_g16": (_i, [_fp, _vp, _fp, _fp, _vp, _i, _i64, _f, _f, _f, _f, _f, _f, _f, _fp, _fp, _vp]),
     "dgtd_adamw_flat_clip": (_i, [_fp, _fp, _vp, _fp, _fp, _vp, _i, _i64, _f, _f, _f, _f, _f, _f, _f, _fp, _fp, _fp, _f, _vp]),
+    "dgtd_adamw_flat_ema": (_i, [_fp, _fp, _vp, _fp, _fp, _vp, _i, _i64, _f, _f, _f, _f, _f, _f, _f, _fp, _fp, _fp, _f, _fp, _fp, _vp]),
+    "dgtd_ema_schedule": (_i, [_fp, _i, _f, _f, _i, _i, _vp]),
+    "dgtd_ema_flat": (_i, [_fp, _fp, _i64, _fp, _vp]),
+    "dgtd_ema_swap": (_i, [_fp, _fp, _vp, _i, _i64, _vp]),
     "dgtd_grad_norm_partial": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp]),
     "dgtd_grad_clip_finalize": (_i, [_vp, _i64, _i, _f, _fp, _fp, _vp]),
     "dgtd_found_inf": (_i, [_fp, _i64, _fp, _vp]),

@@ -6,6 +6,9 @@
 //   g *= inv_scale;  p *= 1 - lr*wd;  m += (1-b1)(g - m);  v = b2 v + (1-b2) g^2;  p -= (lr/bc1) m / (sqrt(v)/sqrt(bc2) + eps);  w = half(p)
 // (the update order of torch's _fused_adamw); the whole launch is a no-op when *found_inf != 0 (GradScaler skips the step).
 // HBM-bound: 28 B/element (+2 with the working copy); 16-byte accesses on the aligned body, scalars on the unaligned head/tail.
+// EMA of the weights (mmengine's EMAHook): the averaged copy of the masters lives in a flat buffer at the same offsets and is updated in
+// the same pass from the master in registers (+8 B/element: one read, one write), with the coefficient of this step read from device
+// memory (dgtd_ema_schedule wrote it), so a captured hipGraph replays the schedule.
 #include "common.h"
 
 namespace {
@@ -22,6 +25,29 @@ __device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, 
 
 enum { CLIP_OFF = 0, CLIP_COEF = 1, CLIP_VALUE = 2 };
 
+// e <- e + c (p - e) over p, e [n]: c == 1 copies (e is not read), c == 0 is the caller's business (it does not call).  Vector accesses on
+// [head, head + 4 body4) - both pointers 16-byte aligned there - and a scalar grid-stride loop over the rest (head == n: all of it).
+__device__ __forceinline__ void ema_range(const float* __restrict__ p, float* __restrict__ e, int64_t n, int64_t head, float c,
+                                          int64_t tid, int64_t nth) {
+  const int64_t body4 = (n - head) / 4;
+  for (int64_t i = tid; i < body4; i += nth) {
+    const int64_t o = head + i * 4;
+    f32x4 pv = *reinterpret_cast<const f32x4*>(p + o);
+    if (c != 1.f) {
+      const f32x4 ev = *reinterpret_cast<const f32x4*>(e + o);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) pv[j] = ev[j] + c * (pv[j] - ev[j]);
+    }
+    *reinterpret_cast<f32x4*>(e + o) = pv;
+  }
+  const int64_t tail0 = head + body4 * 4, nscal = head + (n - tail0);
+  for (int64_t t = tid; t < nscal; t += nth) {
+    const int64_t o = t < head ? t : tail0 + (t - head);
+    const float pj = p[o];
+    e[o] = c == 1.f ? pj : e[o] + c * (pj - e[o]);
+  }
+}
+
 // the un-scaled gradient after clipping: CLIP_COEF multiplies by the global-norm coefficient, CLIP_VALUE clamps to +-c with comparisons
 // that let a NaN through (torch's clamp_); CLIP_OFF is the expression the kernel had before clipping existed
 template <int CLIP>
@@ -31,27 +57,33 @@ __device__ __forceinline__ float clipped(float g, float gs, float c) {
   return g * gs;
 }
 
-template <typename WT, int CLIP>
+template <typename WT, int CLIP, bool EMA>
 __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, WT* __restrict__ w, int64_t n, int64_t head,
                                                          AdamArgs a, const float* __restrict__ amp, const float* __restrict__ lr_dev,
-                                                         const WT* __restrict__ g16, const float* __restrict__ clip_coef, float clip_value) {
+                                                         const WT* __restrict__ g16, const float* __restrict__ clip_coef, float clip_value,
+                                                         float* __restrict__ ema, const float* __restrict__ ema_coef) {
   // g16 != NULL: the gradient is the 16-bit all-reduce payload itself (same phase as w), g is not read
   // amp = the loss scaler's device state { scale, growth_tracker, 1/scale, found_inf, steps taken } or NULL
   // lr_dev = the learning rate in device memory (a captured hipGraph replays with whatever the schedule wrote there) or NULL
   // CLIP_COEF: clip_coef = the device scalar dgtd_grad_clip_finalize wrote; CLIP_VALUE: clip_value = the bound
+  // EMA: ema = the averaged copy of p (same phase), ema_coef = this step's coefficient in device memory (0: ema is left alone)
   float gs = 1.f;
   const float cc = CLIP == CLIP_COEF ? *clip_coef : clip_value;
+  const float ec = EMA ? *ema_coef : 0.f;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
   if (lr_dev) a.lr = *lr_dev;
   if (amp) {
-    if (amp[3] != 0.f) return;                              // overflowed step: parameters, moments and working copies stay as they are
+    if (amp[3] != 0.f) {                                    // overflowed step: parameters, moments and working copies stay as they are
+      if (EMA && ec != 0.f) ema_range(p, ema, n, head, ec, tid, nth);   // mmengine's hook runs after every iteration, skipped or not
+      return;
+    }
     gs = amp[2];
     const float t = amp[4] + 1.f;                           // skipped steps do not advance the bias corrections (GradScaler.step)
     a.inv_bc1 = -1.f / expm1f(t * a.log_b1);
     a.inv_sqrt_bc2 = rsqrtf(-expm1f(t * a.log_b2));
   }
   typedef typename Vec8<WT>::type W4;
-  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
   const int64_t body4 = (n - head) / 4;                      // float4 groups after the unaligned head
   for (int64_t i = tid; i < body4; i += nth) {
     const int64_t o = head + i * 4;
@@ -75,6 +107,14 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
       for (int j = 0; j < 4; ++j) wv[j] = (WT)pv[j];
       *reinterpret_cast<W4*>(w + o) = wv;
     }
+    if (EMA && ec != 0.f) {                                  // uniform: one coefficient for the whole launch
+      if (ec != 1.f) {
+        const f32x4 ev = *reinterpret_cast<const f32x4*>(ema + o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pv[j] = ev[j] + ec * (pv[j] - ev[j]);
+      }
+      *reinterpret_cast<f32x4*>(ema + o) = pv;
+    }
   }
   // head [0, head) and tail [head + 4*body4, n): at most 6 scalars
   const int64_t tail0 = head + body4 * 4;
@@ -85,7 +125,59 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
     const float pj = adam_one(p[o], clipped<CLIP>(g16 ? (float)g16[o] : g[o], gs, cc), mj, vj, a);
     p[o] = pj; m[o] = mj; v[o] = vj;
     if (w) w[o] = (WT)pj;
+    if (EMA && ec != 0.f) ema[o] = ec == 1.f ? pj : ema[o] + ec * (pj - ema[o]);
   }
+}
+
+// the EMA update alone (stretches AdamW does not visit, float buffers)
+__global__ __launch_bounds__(256) void ema_flat_kernel(const float* __restrict__ p, float* __restrict__ e, int64_t n, int64_t head,
+                                                       const float* __restrict__ ema_coef) {
+  const float c = *ema_coef;
+  if (c == 0.f) return;
+  ema_range(p, e, n, head, c, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
+}
+
+// p <-> e in place; w (16-bit working copy of p, same phase, or NULL) is rewritten from the new p
+template <typename WT>
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ e, WT* __restrict__ w, int64_t n, int64_t head) {
+  typedef typename Vec8<WT>::type W4;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+  const int64_t body4 = (n - head) / 4;
+  for (int64_t i = tid; i < body4; i += nth) {
+    const int64_t o = head + i * 4;
+    const f32x4 pv = *reinterpret_cast<const f32x4*>(p + o), ev = *reinterpret_cast<const f32x4*>(e + o);
+    *reinterpret_cast<f32x4*>(p + o) = ev;
+    *reinterpret_cast<f32x4*>(e + o) = pv;
+    if (w) {
+      W4 wv;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wv[j] = (WT)ev[j];
+      *reinterpret_cast<W4*>(w + o) = wv;
+    }
+  }
+  const int64_t tail0 = head + body4 * 4, nscal = head + (n - tail0);
+  for (int64_t t = tid; t < nscal; t += nth) {
+    const int64_t o = t < head ? t : tail0 + (t - head);
+    const float pj = p[o], ej = e[o];
+    p[o] = ej; e[o] = pj;
+    if (w) w[o] = (WT)ej;
+  }
+}
+
+// mmengine's EMAHook / BaseAveragedModel schedule on the device: state = { coef of this step, steps (updates counted), iters seen, enabled }.
+__global__ void ema_schedule_kernel(float* __restrict__ state, int kind, float momentum, float gamma, int interval, int begin_iter) {
+  float coef = 1.f, steps = state[1];                       // before begin_iter / while disabled the average is a copy of the weights
+  const float iters = state[2];
+  if (state[3] != 0.f && iters >= (float)begin_iter) {
+    const int k = (int)steps;
+    if (k == 0) coef = 1.f;
+    else if (k % interval != 0) coef = 0.f;
+    else if (kind == 0) coef = momentum;
+    else if (kind == 1) coef = fmaxf(momentum, (float)((double)gamma / ((double)gamma + (double)k)));
+    else coef = (float)(1.0 / (double)(k / interval + 1));
+    steps += 1.f;
+  }
+  state[0] = coef; state[1] = steps; state[2] = iters + 1.f;
 }
 
 // found[0] = 1 if any element of g[0, n) is inf or NaN (left untouched otherwise): the `found_inf` of GradScaler.unscale_.
@@ -201,20 +293,21 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, float growth
 
 }  // namespace
 
-template <typename WT>
+template <typename WT, bool EMA>
 static void adamw_launch(int clip, int grid, hipStream_t st, float* p, const float* g, float* m, float* v, WT* w, int64_t n, int64_t head, AdamArgs a,
-                         const float* amp, const float* lr_dev, const WT* g16, const float* clip_coef, float clip_value) {
-  if (clip == CLIP_COEF) hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_COEF>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value);
-  else if (clip == CLIP_VALUE) hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_VALUE>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value);
-  else hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_OFF>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value);
+                         const float* amp, const float* lr_dev, const WT* g16, const float* clip_coef, float clip_value, float* ema, const float* ema_coef) {
+  if (clip == CLIP_COEF) hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_COEF, EMA>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value, ema, ema_coef);
+  else if (clip == CLIP_VALUE) hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_VALUE, EMA>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value, ema, ema_coef);
+  else hipLaunchKernelGGL((adamw_flat_kernel<WT, CLIP_OFF, EMA>), dim3(grid), dim3(256), 0, st, p, g, m, v, w, n, head, a, amp, lr_dev, g16, clip_coef, clip_value, ema, ema_coef);
 }
 
 static int adamw_impl(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr, float beta1,
                       float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
-                      const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, dgtd_stream s) {
+                      const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, float* ema,
+                      const float* ema_coef_dev, dgtd_stream s) {
   const int clip = clip_coef_dev ? CLIP_COEF : (clip_value > 0.f ? CLIP_VALUE : CLIP_OFF);
-  DGTD_PROF(s, DGTD_HBM, (w ? 30.0 : 28.0) * n - (g16 ? 2.0 * n : 0.0), "dgtd_adamw_flat[n=%lld%s%s]", (long long)n, g16 ? ",g16" : "",
-            clip == CLIP_COEF ? ",clip=norm" : (clip == CLIP_VALUE ? ",clip=value" : ""));
+  DGTD_PROF(s, DGTD_HBM, (w ? 30.0 : 28.0) * n - (g16 ? 2.0 * n : 0.0) + (ema ? 8.0 * n : 0.0), "dgtd_adamw_flat[n=%lld%s%s%s]", (long long)n,
+            g16 ? ",g16" : "", clip == CLIP_COEF ? ",clip=norm" : (clip == CLIP_VALUE ? ",clip=value" : ""), ema ? ",ema" : "");
   DGTD_REQUIRE(n > 0 && p && (g || g16) && m && v, "adamw_flat: bad arguments");
   DGTD_REQUIRE(!(clip_coef_dev && clip_value > 0.f), "adamw_flat: clip by norm (clip_coef_dev) and by value (clip_value > 0) exclude each other");
   if (!g) g = p;                                                             // never read; keeps the phase checks below trivially true
@@ -225,10 +318,12 @@ static int adamw_impl(float* p, const float* g, const void* g16, float* m, float
   DGTD_REQUIRE(((uintptr_t)g - ap) % 16 == 0 && ((uintptr_t)m - ap) % 16 == 0 && ((uintptr_t)v - ap) % 16 == 0 && ap % 4 == 0,
                "adamw_flat: p, g, m, v must share their 16-byte phase");
   DGTD_REQUIRE(!w || (((uintptr_t)w % 8) * 2 == ap % 16), "adamw_flat: the working copy must share the phase of the masters");
+  DGTD_REQUIRE(!ema || (ema_coef_dev && ((uintptr_t)ema - ap) % 16 == 0), "adamw_flat: the average needs its coefficient and must share the phase of the masters");
   const int64_t head = std::min<int64_t>(n, ((16 - (int64_t)(ap % 16)) % 16) / 4);
   AdamArgs a{lr, beta1, beta2, eps, weight_decay, 1.f / bias_correction1, 1.f / sqrtf(bias_correction2), (float)log((double)beta1), (float)log((double)beta2)};
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((n + 3) / 4 + 8, 256), 8192));
-  DGTD_DISPATCH_HALF(w_dt, adamw_launch<T_>(clip, grid, (hipStream_t)s, p, g, m, v, (T_*)w, n, head, a, amp_state, lr_dev, (const T_*)g16, clip_coef_dev, clip_value));
+  if (ema) DGTD_DISPATCH_HALF(w_dt, (adamw_launch<T_, true>(clip, grid, (hipStream_t)s, p, g, m, v, (T_*)w, n, head, a, amp_state, lr_dev, (const T_*)g16, clip_coef_dev, clip_value, ema, ema_coef_dev)));
+  else DGTD_DISPATCH_HALF(w_dt, (adamw_launch<T_, false>(clip, grid, (hipStream_t)s, p, g, m, v, (T_*)w, n, head, a, amp_state, lr_dev, (const T_*)g16, clip_coef_dev, clip_value, nullptr, nullptr)));
   DGTD_CHECK_LAUNCH("adamw_flat");
   return 0;
 }
@@ -237,14 +332,14 @@ extern "C" int dgtd_adamw_flat_amp(float* p, const float* g, float* m, float* v,
                                    float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
                                    const float* amp_state, const float* lr_dev, dgtd_stream s) {
   DGTD_REQUIRE(g, "adamw_flat: bad arguments");
-  return adamw_impl(p, g, nullptr, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, nullptr, 0.f, s);
+  return adamw_impl(p, g, nullptr, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, nullptr, 0.f, nullptr, nullptr, s);
 }
 
 extern "C" int dgtd_adamw_flat_g16(float* p, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr, float beta1,
                                    float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
                                    const float* amp_state, const float* lr_dev, dgtd_stream s) {
   DGTD_REQUIRE(g16, "adamw_flat_g16: bad arguments");
-  return adamw_impl(p, nullptr, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, nullptr, 0.f, s);
+  return adamw_impl(p, nullptr, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev, nullptr, 0.f, nullptr, nullptr, s);
 }
 
 extern "C" int dgtd_adamw_flat(float* p, const float* g, float* m, float* v, void* w_bf16, int64_t n, float lr, float beta1, float beta2,
@@ -258,7 +353,59 @@ extern "C" int dgtd_adamw_flat_clip(float* p, const float* g, const void* g16, f
                                     const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, dgtd_stream s) {
   DGTD_REQUIRE((g != nullptr) != (g16 != nullptr), "adamw_flat_clip: exactly one of g (fp32) and g16 (16-bit payload) is given");
   return adamw_impl(p, g, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev,
-                    clip_coef_dev, clip_value, s);
+                    clip_coef_dev, clip_value, nullptr, nullptr, s);
+}
+
+extern "C" int dgtd_adamw_flat_ema(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
+                                   const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, float* ema,
+                                   const float* ema_coef_dev, dgtd_stream s) {
+  DGTD_REQUIRE((g != nullptr) != (g16 != nullptr), "adamw_flat_ema: exactly one of g (fp32) and g16 (16-bit payload) is given");
+  return adamw_impl(p, g, g16, m, v, w, w_dt, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, amp_state, lr_dev,
+                    clip_coef_dev, clip_value, ema, ema ? ema_coef_dev : nullptr, s);
+}
+
+// head of the 16-byte body shared by p and e, or n (everything scalar) when their phases differ
+static int64_t ema_head(const float* p, const float* e, int64_t n) {
+  const uintptr_t ap = (uintptr_t)p;
+  if (((uintptr_t)e - ap) % 16 != 0) return n;
+  return std::min<int64_t>(n, ((16 - (int64_t)(ap % 16)) % 16) / 4);
+}
+
+extern "C" int dgtd_ema_flat(const float* p, float* ema, int64_t n, const float* ema_coef_dev, dgtd_stream s) {
+  DGTD_PROF(s, DGTD_HBM, 12.0 * n, "dgtd_ema_flat[n=%lld]", (long long)n);
+  DGTD_REQUIRE(n > 0 && p && ema && ema_coef_dev, "ema_flat: bad arguments");
+  DGTD_REQUIRE((uintptr_t)p % 4 == 0 && (uintptr_t)ema % 4 == 0, "ema_flat: p and ema must be 4-byte aligned");
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((n + 3) / 4 + 8, 256), 8192));
+  hipLaunchKernelGGL(ema_flat_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, p, ema, n, ema_head(p, ema, n), ema_coef_dev);
+  DGTD_CHECK_LAUNCH("ema_flat");
+  return 0;
+}
+
+template <typename WT>
+static void ema_swap_launch(int grid, hipStream_t st, float* p, float* ema, void* w, int64_t n, int64_t head) {
+  hipLaunchKernelGGL(ema_swap_kernel<WT>, dim3(grid), dim3(256), 0, st, p, ema, (WT*)w, n, head);
+}
+
+extern "C" int dgtd_ema_swap(float* p, float* ema, void* w, dgtd_dtype w_dt, int64_t n, dgtd_stream s) {
+  DGTD_PROF(s, DGTD_HBM, (w ? 18.0 : 16.0) * n, "dgtd_ema_swap[n=%lld]", (long long)n);
+  DGTD_REQUIRE(n > 0 && p && ema && p != ema, "ema_swap: bad arguments");
+  DGTD_REQUIRE((uintptr_t)p % 4 == 0 && (uintptr_t)ema % 4 == 0, "ema_swap: p and ema must be 4-byte aligned");
+  DGTD_REQUIRE(!w || DGTD_IS_HALF(w_dt), "ema_swap: the working copy is bf16 or fp16, got dtype %d", (int)w_dt);
+  DGTD_REQUIRE(!w || (((uintptr_t)ema - (uintptr_t)p) % 16 == 0 && ((uintptr_t)w % 8) * 2 == (uintptr_t)p % 16),
+               "ema_swap: with a working copy p, ema and w must share their 16-byte phase");
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv((n + 3) / 4 + 8, 256), 8192));
+  DGTD_DISPATCH_HALF(w_dt, ema_swap_launch<T_>(grid, (hipStream_t)s, p, ema, w, n, ema_head(p, ema, n)));
+  DGTD_CHECK_LAUNCH("ema_swap");
+  return 0;
+}
+
+extern "C" int dgtd_ema_schedule(float* ema_state, int kind, float momentum, float gamma, int interval, int begin_iter, dgtd_stream s) {
+  DGTD_REQUIRE(ema_state && kind >= 0 && kind <= 2 && momentum > 0.f && momentum < 1.f && gamma > 0.f && interval >= 1 && begin_iter >= 0,
+               "ema_schedule: bad arguments");
+  hipLaunchKernelGGL(ema_schedule_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, ema_state, kind, momentum, gamma, interval, begin_iter);
+  DGTD_CHECK_LAUNCH("ema_schedule");
+  return 0;
 }
 
 template <typename T>

@@ -1,5 +1,5 @@
 """Minimal pieces of the training loop the reference delegates to nest/mmengine."""
-from .optim import FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, lr_mult_for, parse_clip_grad  # noqa: F401
+from .optim import EmaTorch, FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, ema_coefficient, lr_mult_for, parse_clip_grad, parse_ema  # noqa: F401
 from .data import DefaultSampler, SyntheticRGBD, batches, device_preprocess, device_sample
 from . import metrics  # noqa: F401  # noqa: F401
 from .checkpoint import load_checkpoint, load_checkpoint_file, load_pretrained, save_checkpoint  # noqa: F401

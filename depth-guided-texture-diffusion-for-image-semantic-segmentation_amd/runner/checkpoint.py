@@ -45,9 +45,18 @@ def load_checkpoint(model: torch.nn.Module, path: str, map_location="cpu", stric
     return model.load_state_dict(_unwrap(ckpt, "state_dict"), strict=strict)
 
 
-def save_checkpoint(model: torch.nn.Module, path: str, optimizer=None, schedulers=None, meta: Optional[dict] = None) -> None:
+def save_checkpoint(model: torch.nn.Module, path: str, optimizer=None, schedulers=None, meta: Optional[dict] = None,
+                    ema: Optional[tuple] = None) -> None:
+    """``ema`` = (averaged tensors by state_dict key, steps) writes mmengine's EMAHook layout: ``ema_state_dict`` = the model's own
+    (raw) entries under ``module.<key>`` plus ``steps``, and ``state_dict`` with the averaged tensor in place of every entry that has
+    one - the two exchanged, as EMAHook.before_save_checkpoint leaves them, so whoever loads ``state_dict`` gets the averaged model."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     out = {"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "meta": dict(meta or {})}
+    if ema is not None:
+        avg, steps = ema
+        out["ema_state_dict"] = {"module." + k: v for k, v in out["state_dict"].items()}
+        out["ema_state_dict"]["steps"] = torch.tensor(int(steps), dtype=torch.long)
+        out["state_dict"] = {k: (avg[k].detach().cpu().contiguous().clone() if k in avg else v.clone()) for k, v in out["state_dict"].items()}
     if optimizer is not None:
         out["optimizer"] = optimizer.state_dict()
     if schedulers is not None:

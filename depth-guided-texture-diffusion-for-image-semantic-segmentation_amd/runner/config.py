@@ -2,7 +2,7 @@
 ``train_cfg`` (by_epoch, max_epochs, val_interval), ``train_dataloader.batch_size``, ``model.type`` (+ kwargs the reference
 ignores, cod.py:38-46), ``optim_wrapper`` (AdamW, ``paramwise_cfg.custom_keys`` lr_mult, bypass_duplicate, ``clip_grad`` by norm or by value),
 ``param_scheduler`` (CosineAnnealingLR by epoch), ``default_hooks.logger.interval`` / ``checkpoint.interval``,
-``custom_hooks: our_init``, ``*_dataloader.sampler`` (DefaultSampler), ``val_evaluator``, ``optim_wrapper.type: AmpOptimWrapper``
+``custom_hooks: our_init`` and ``EMAHook`` (validate and checkpoint with the moving average of the weights), ``*_dataloader.sampler`` (DefaultSampler), ``val_evaluator``, ``optim_wrapper.type: AmpOptimWrapper``
 (= fp16 autocast + dynamic loss scaling when the runner is built with ``compute_dtype=torch.float16``).  The external nest/mmengine runner is out of scope; this is what drives the HIP-backed model from
 the same file.  ``model:`` keys beyond ``type`` reach the model class as keyword arguments (``build_model``), so
 ``model: {type: cod, diffuser: {grid: 22, k: 5, max_step: 6}}`` selects a texture-diffuser configuration (keys ``grid``, ``k``, ``max_step``,
@@ -19,7 +19,7 @@ import yaml
 from .checkpoint import load_checkpoint_file, load_pretrained, save_checkpoint
 from .data import DefaultSampler, batches
 from .metrics import build_evaluators
-from .optim import FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, parse_clip_grad
+from .optim import EmaTorch, FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, parse_clip_grad, parse_ema
 
 MODEL_REGISTRY: Dict[str, Callable] = {}
 
@@ -110,14 +110,23 @@ class Runner:
         # optim_wrapper.clip_grad (config/cod.yml:108-110): inside FlatAdamW on the HIP device, torch's utilities before torch.optim.AdamW on CPU
         self.clip_grad = parse_clip_grad(ow.get("clip_grad"))
         self._grad_norm = None
+        # custom_hooks: EMAHook (mmengine): train with the raw weights, validate and checkpoint with their moving average.  Inside
+        # FlatAdamW on the HIP device, EmaTorch beside torch.optim.AdamW on CPU; self.ema is whichever carries it, or None without the hook
+        ema_hooks = [h for h in cfg.get("custom_hooks") or [] if h.get("type") == "EMAHook"]
+        if len(ema_hooks) > 1:
+            raise ValueError("custom_hooks holds more than one EMAHook")
+        self.ema_cfg = parse_ema(ema_hooks[0]) if ema_hooks else None
+        self.ema = None
         if on_gpu:
             if compute_dtype == torch.float16:
                 assert ow.get("type") == "AmpOptimWrapper", "fp16 compute needs the AmpOptimWrapper recipe (loss scaling)"
                 self.scaler = LossScaler(device)
             self.optimizer = FlatAdamW(self.reducer, lr=float(ocfg["lr"]), weight_decay=float(ocfg.get("weight_decay", 0.0)),
-                                       custom_keys=custom_keys_of(cfg), scaler=self.scaler, clip_grad=self.clip_grad)
+                                       custom_keys=custom_keys_of(cfg), scaler=self.scaler, clip_grad=self.clip_grad, ema=ema_hooks[0] if ema_hooks else None, module=self.model)
+            self.ema = self.optimizer if self.ema_cfg is not None else None
         else:
             self.optimizer = build_optim(cfg, self.model)
+            self.ema = EmaTorch(self.model, ema_hooks[0]) if ema_hooks else None
         tc = cfg["train_cfg"]
         self.max_epochs = int(tc["max_epochs"])
         self.val_interval = int(tc.get("val_interval", 0) or 0)
@@ -130,6 +139,26 @@ class Runner:
         self.sod_metrics = sod_metrics or (cfg.get("val_cfg") or {}).get("sod_metrics") or "skip"
         self.evaluators = build_evaluators(cfg.get("val_evaluator"), log, sod_metrics=self.sod_metrics)
         self.epoch = 0
+        self._ema_gate()
+
+    # ------------------------------------------------------------------ EMA of the weights
+    def _ema_gate(self) -> None:
+        """``begin_epoch``: until then the average stays a copy of the weights (the flag travels to the device with the next step)."""
+        if self.ema is not None and self.ema_cfg["begin_epoch"]:
+            self.ema.set_ema_enabled(self.epoch >= self.ema_cfg["begin_epoch"])
+
+    def swap_ema(self) -> None:
+        """Exchange the model's weights with their average, in place (and back with a second call)."""
+        self.ema.swap_ema()
+        if not isinstance(self.optimizer, FlatAdamW):
+            self.reducer.refresh_working()
+
+    def _ema_by_key(self) -> Dict[str, torch.Tensor]:
+        """The averages under every state_dict key they stand for (a shared parameter is averaged once, under its first name)."""
+        avg, first, alias = self.ema.ema_tensors(), {}, {}
+        for n, p in self.model.named_parameters(remove_duplicate=False):
+            alias[n] = first.setdefault(id(p), n)
+        return {k: avg[alias.get(k, k)] for k in self.model.state_dict() if alias.get(k, k) in avg}
 
     # ------------------------------------------------------------------ data
     def loader(self, dataset, split: str = "train", epoch: int = 0):
@@ -149,9 +178,13 @@ class Runner:
         self.reducer.finish()
         if self.clip_grad is not None and not isinstance(self.optimizer, FlatAdamW):
             self._grad_norm = clip_grad_torch((p for g in self.optimizer.param_groups for p in g["params"]), self.clip_grad)
+        if self.ema is self.optimizer:
+            self.optimizer.sync_ema()
         self.optimizer.step()
         if not isinstance(self.optimizer, FlatAdamW):
             self.reducer.refresh_working()
+            if self.ema is not None:
+                self.ema.update()
         return loss
 
     def grad_norm(self):
@@ -166,6 +199,7 @@ class Runner:
         losses = []
         for epoch in range(self.epoch, epochs or self.max_epochs):
             self.model.train()
+            self._ema_gate()
             for it, batch in enumerate(loader_fn(epoch)):
                 loss = self.train_step(batch)
                 losses.append(loss.detach())
@@ -195,10 +229,16 @@ class Runner:
             ev.__dict__.pop("_all", None)
             if callable(getattr(ev, "reset", None)):
                 ev.reset()
-        for batch in loader:
-            out = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="predict")
-            for ev in self.evaluators:
-                ev.process(batch, out)
+        if self.ema is not None:          # EMAHook.before_val_epoch / after_val_epoch: validate with the averaged weights
+            self.swap_ema()
+        try:
+            for batch in loader:
+                out = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="predict")
+                for ev in self.evaluators:
+                    ev.process(batch, out)
+        finally:
+            if self.ema is not None:
+                self.swap_ema()
         self.model.train(was_training)
         metrics = {}
         for ev in self.evaluators:
@@ -207,15 +247,36 @@ class Runner:
 
     # ------------------------------------------------------------------ checkpoint / resume
     def save(self, path: str) -> None:
-        save_checkpoint(self.model, path, self.optimizer, [self.scheduler] if self.scheduler else None, {"epoch": self.epoch})
+        if self.ema is None:
+            save_checkpoint(self.model, path, self.optimizer, [self.scheduler] if self.scheduler else None, {"epoch": self.epoch})
+            return
+        # EMAHook.before_save_checkpoint: ``state_dict`` carries the AVERAGED weights (what our_init.before_val and every plain loader
+        # read), ``ema_state_dict`` the raw ones under ``module.*`` plus ``steps``
+        save_checkpoint(self.model, path, self.optimizer, [self.scheduler] if self.scheduler else None,
+                        {"epoch": self.epoch, "iter": self.ema.ema_iters}, ema=(self._ema_by_key(), self.ema.ema_steps))
 
     def resume(self, path: str) -> None:
         """Continue a run: weights (the reducer's load hooks refresh the working copies), optimizer state (moments, step, loss
-        scale), scheduler and epoch."""
+        scale), scheduler and epoch.  With EMAHook the two entries of the file are exchanged back: ``ema_state_dict`` (raw) goes into
+        the model, ``state_dict`` into the average; a file without ``ema_state_dict`` starts the average from its ``state_dict``
+        (``strict_load``: raises)."""
         ckpt = load_checkpoint_file(path, weights_only=False)
-        self.model.load_state_dict(ckpt["state_dict"], strict=True)
+        if self.ema is None:
+            self.model.load_state_dict(ckpt["state_dict"], strict=True)
+        else:
+            sd, esd = ckpt["state_dict"], ckpt.get("ema_state_dict")
+            iters = int((ckpt.get("meta") or {}).get("iter", 0))
+            if esd is None:
+                if self.ema_cfg["strict_load"]:
+                    raise KeyError(f"{path} has no ema_state_dict (EMAHook strict_load)")
+                self.model.load_state_dict(sd, strict=True)
+                self.ema.load_ema(None, 0, iters)
+            else:
+                self.model.load_state_dict({k: esd["module." + k] for k in sd}, strict=True)
+                self.ema.load_ema(sd, int(esd["steps"]), iters)
         if "optimizer" in ckpt:
             self.optimizer.load_state_dict(ckpt["optimizer"])
         if self.scheduler is not None and ckpt.get("param_schedulers"):
             self.scheduler.load_state_dict(ckpt["param_schedulers"][0])
         self.epoch = int((ckpt.get("meta") or {}).get("epoch", 0))
+        self._ema_gate()

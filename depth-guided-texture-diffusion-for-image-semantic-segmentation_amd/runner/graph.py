@@ -208,6 +208,9 @@ class GraphedTrainStep:
                 "moments": [(st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for st in o.state],
                 "opt_state": None if o._state is None else o._state.clone(), "steps": o._steps,
                 "buffers": [(bf, bf.clone()) for bf in self.net.buffers()],
+                # the averages of FlatAdamW(ema=...) and their schedule state: the warm-up steps leave no trace in them either
+                "ema": [(e, e.clone()) for e in list(getattr(o, "ema_bufs", ())) + [t for _, _, t in getattr(o, "_ema_named_buffers", ())]
+                        + ([o.ema_state] if getattr(o, "ema_state", None) is not None else [])],
                 "rng": torch.cuda.get_rng_state(), "cpu_rng": torch.get_rng_state()}
         return snap
 
@@ -224,7 +227,7 @@ class GraphedTrainStep:
         if snap["opt_state"] is not None:
             o._state.copy_(snap["opt_state"])
         o._steps = snap["steps"]
-        for bf, v in snap["buffers"]:
+        for bf, v in snap["buffers"] + snap["ema"]:
             bf.copy_(v)
         torch.cuda.set_rng_state(snap["rng"])
         torch.set_rng_state(snap["cpu_rng"])
@@ -325,6 +328,7 @@ class GraphedTrainStep:
         if self.graph_fb is None:
             self.capture(batch)
         self.opt.sync_lr()
+        self.opt.sync_ema()               # the EMA's enabled flag (begin_epoch) reaches the device the same way
         self._stage(batch)
         self.graph_fb.replay()
         if self.split:

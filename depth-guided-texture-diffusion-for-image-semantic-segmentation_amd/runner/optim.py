@@ -92,6 +92,135 @@ def clip_grad_torch(params: Iterable[torch.Tensor], clip_grad: Optional[dict]) -
     return None
 
 
+EMA_TYPES = ("ExponentialMovingAverage", "MomentumAnnealingEMA", "StochasticWeightAverage")      # kind 0, 1, 2 of dgtd_ema_schedule
+
+
+def parse_ema(ema: Optional[dict]) -> Optional[dict]:
+    """mmengine's ``EMAHook`` entry of ``custom_hooks`` (or the same keys without ``type``) -> a normal form with every key present, or
+    ValueError; ``None`` -> ``None``.  Keys: ``ema_type`` (one of ``EMA_TYPES``), ``momentum`` in (0, 1), ``gamma`` > 0 (only with
+    MomentumAnnealingEMA), ``interval`` >= 1, ``update_buffers``, ``begin_iter`` >= 0, ``begin_epoch`` >= 0 (not both non-zero),
+    ``strict_load``; ``type`` (must be EMAHook) and ``priority`` are the hook's own and carry nothing."""
+    if ema is None:
+        return None
+    if not isinstance(ema, dict):
+        raise ValueError(f"ema must be a dict, got {ema!r}")
+    if ema.get("type", "EMAHook") != "EMAHook":
+        raise ValueError(f"ema.type must be 'EMAHook', got {ema.get('type')!r}")
+    extra = set(ema) - {"type", "priority", "ema_type", "momentum", "gamma", "interval", "update_buffers", "begin_iter", "begin_epoch", "strict_load"}
+    if extra:
+        raise ValueError(f"EMAHook does not take {sorted(extra)}")
+    ema_type = ema.get("ema_type", EMA_TYPES[0])
+    if ema_type not in EMA_TYPES:
+        raise ValueError(f"ema.ema_type must be one of {EMA_TYPES}, got {ema_type!r}")
+
+    def number(key, default, ok, what, integer=False):
+        v = ema.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, int if integer else (int, float)) or not ok(v):
+            raise ValueError(f"ema.{key} must be {what}, got {v!r}")
+        return int(v) if integer else float(v)
+
+    def flag(key):
+        v = ema.get(key, False)
+        if not isinstance(v, bool):
+            raise ValueError(f"ema.{key} must be true or false, got {v!r}")
+        return v
+    if "gamma" in ema and ema_type != "MomentumAnnealingEMA":
+        raise ValueError(f"ema.gamma belongs to MomentumAnnealingEMA, not to {ema_type}")
+    out = {"ema_type": ema_type, "kind": EMA_TYPES.index(ema_type),
+           "momentum": number("momentum", 0.0002, lambda v: 0.0 < v < 1.0, "in (0, 1)"),
+           "gamma": number("gamma", 100, lambda v: v > 0 and not math.isinf(v), "a positive finite number"),
+           "interval": number("interval", 1, lambda v: v >= 1, "an integer >= 1", integer=True),
+           "update_buffers": flag("update_buffers"),
+           "begin_iter": number("begin_iter", 0, lambda v: v >= 0, "an integer >= 0", integer=True),
+           "begin_epoch": number("begin_epoch", 0, lambda v: v >= 0, "an integer >= 0", integer=True),
+           "strict_load": flag("strict_load")}
+    if out["begin_iter"] and out["begin_epoch"]:
+        raise ValueError("ema: begin_iter and begin_epoch exclude each other")
+    return out
+
+
+def ema_coefficient(cfg: dict, steps: int) -> float:
+    """``c(kind, steps)`` of the schedule: the weight of the current parameters in the update that follows ``steps`` counted ones."""
+    if cfg["kind"] == 0:
+        return cfg["momentum"]
+    if cfg["kind"] == 1:
+        return max(cfg["momentum"], cfg["gamma"] / (cfg["gamma"] + steps))
+    return 1.0 / (steps // cfg["interval"] + 1)
+
+
+class EmaTorch:
+    """The CPU path of ``EMAHook`` (beside torch.optim.AdamW): the schedule of ``dgtd_ema_schedule`` on the host and the update
+    ``e += c (p - e)`` in torch ops, over the parameters of ``model`` (shared ones once) and - ``update_buffers`` - its float buffers.
+    Same surface as ``FlatAdamW(ema=...)``: ``update()`` once per iteration, ``ema_steps``, ``swap_ema()``, ``ema_tensors()``, ``load_ema()``."""
+
+    def __init__(self, model: Optional[torch.nn.Module], ema: dict):
+        self.ema = parse_ema(ema)
+        if self.ema is None:
+            raise ValueError("EmaTorch needs an EMAHook configuration")
+        self.coef, self.steps, self.iters, self.enabled = 1.0, 0, 0, True
+        self.live: Dict[str, torch.Tensor] = {}
+        if model is not None:
+            seen = set()
+            for n, p in model.named_parameters():
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    self.live[n] = p
+            if self.ema["update_buffers"]:
+                self.live.update({n: b for n, b in model.named_buffers() if b.is_floating_point()})
+        self.avg = {n: t.detach().clone() for n, t in self.live.items()}
+
+    def schedule(self) -> float:
+        """One iteration of the table in include/dgtd.h; returns (and keeps) the coefficient."""
+        c = 1.0
+        if self.enabled and self.iters >= self.ema["begin_iter"]:
+            k = self.steps
+            c = 1.0 if k == 0 else (ema_coefficient(self.ema, k) if k % self.ema["interval"] == 0 else 0.0)
+            self.steps += 1
+        self.iters += 1
+        self.coef = c
+        return c
+
+    @torch.no_grad()
+    def update(self) -> None:
+        c = self.schedule()
+        if c == 0.0:
+            return
+        for n, p in self.live.items():
+            e = self.avg[n]
+            if c == 1.0:
+                e.copy_(p)
+            else:
+                e.add_(p.detach() - e, alpha=c)
+
+    @property
+    def ema_steps(self) -> int:
+        return self.steps
+
+    @property
+    def ema_iters(self) -> int:
+        return self.iters
+
+    def set_ema_enabled(self, on: bool) -> None:
+        self.enabled = bool(on)
+
+    @torch.no_grad()
+    def swap_ema(self) -> None:
+        for n, p in self.live.items():
+            t = p.detach().clone()
+            p.copy_(self.avg[n])
+            self.avg[n].copy_(t)
+
+    def ema_tensors(self) -> Dict[str, torch.Tensor]:
+        return dict(self.avg)
+
+    @torch.no_grad()
+    def load_ema(self, named: Optional[dict], steps: int = 0, iters: int = 0) -> None:
+        """``named`` = averaged tensors by state_dict key (others are ignored), or ``None``: the average restarts as a copy of the weights."""
+        for n, e in self.avg.items():
+            e.copy_(self.live[n] if named is None else named[n])
+        self.steps, self.iters = int(steps), int(iters)
+
+
 class LossScaler:
     """Dynamic loss scaling with torch.amp.GradScaler's rule (the reference's AmpOptimWrapper, config/sod.yml:57): the loss is
     multiplied by ``scale``; a step whose gradients hold an inf / NaN is skipped and halves the scale, ``growth_interval`` clean
@@ -140,14 +269,26 @@ class FlatAdamW:
     launched.  A global norm needs every bucket: under ``pipelined`` each bucket's norm launch still waits for that bucket's all-reduce
     only, but the finalize and with it every AdamW launch come after the last bucket, so AdamW of the first buckets no longer overlaps
     the later all-reduces.  All-reduced gradients are identical on every rank, so the norm needs no collective of its own.
-    Clip by value: only an argument of the AdamW launches changes."""
+    Clip by value: only an argument of the AdamW launches changes.
+    ``ema``: mmengine's ``EMAHook`` (see ``parse_ema``): an exponential moving average of the masters in one flat fp32 buffer per bucket
+    (``ema_bufs``, +4 B/parameter), updated inside the AdamW launches (``dgtd_adamw_flat_ema``) with the coefficient ``dgtd_ema_schedule``
+    leaves in ``ema_state`` (device, { coef, steps, iters, enabled }) once per step: nothing of it is a host value, so the captured step
+    replays it.  Stretches AdamW does not visit (world 1: slots without a gradient) get ``dgtd_ema_flat``, so every element of every
+    average sees exactly one update per step; an overflowed fp16 step still updates the average (against the unchanged masters).
+    ``update_buffers``: the float buffers of ``module`` (the model the reducer was built over; required then, and only its buffer
+    tensors are kept: the model's leaves hold the reducer through autograd hooks the cycle collector cannot see, so a reference back
+    to the model would keep both alive) are averaged too, one ``dgtd_ema_flat`` each; otherwise the averaged model shares the live
+    buffers.  ``swap_ema()`` exchanges masters and averages in place (working copies rewritten)."""
 
     def __init__(self, reducer, lr: float = 5e-4, weight_decay: float = 0.1, betas=(0.9, 0.999), eps: float = 1e-8,
                  custom_keys: Optional[Dict[str, float]] = None, scaler: Optional[LossScaler] = None, graph_safe: bool = False,
-                 clip_grad: Optional[dict] = None):
+                 clip_grad: Optional[dict] = None, ema: Optional[dict] = None, module: Optional[torch.nn.Module] = None):
         from .. import _lib as L
         self._L = L
         self.clip_grad = parse_clip_grad(clip_grad)      # ValueError before anything is built
+        self.ema = parse_ema(ema)
+        if self.ema is not None and self.ema["update_buffers"] and module is None:
+            raise ValueError("ema.update_buffers needs module=: the model whose float buffers are averaged")
         self.reducer, self.scaler = reducer, scaler
         custom_keys = SOD_CUSTOM_KEYS if custom_keys is None else custom_keys
         self.betas, self.eps, self.weight_decay, self._steps = betas, eps, weight_decay, 0
@@ -184,6 +325,88 @@ class FlatAdamW:
             self._clip_state = torch.zeros(2, dtype=torch.float32, device=dev)
             self._norm_ws = torch.zeros(max(1, sum(self._norm_grid(n) for slots in self.slots for _, n, _ in slots)), dtype=torch.float64, device=dev)
             self._norm_kind = 1 if math.isinf(self.clip_grad["norm_type"]) else 0
+        # EMA: the averages start as copies of the masters (the padding stays zero), the state as { coef 1, 0 steps, 0 iters, enabled }
+        self.ema_bufs, self.ema_state, self._ema_named_buffers, self._ema_enabled, self._ema_want = [], None, [], True, True
+        if self.ema is not None:
+            for b in reducer.buckets:
+                e = torch.zeros_like(b["mflat"])
+                e.copy_(b["mflat"])
+                self.ema_bufs.append(e)
+            self.ema_state = torch.tensor([1.0, 0.0, 0.0, 1.0], dtype=torch.float32, device=dev)
+            if self.ema["update_buffers"]:
+                self._ema_named_buffers = [(n, bf, bf.detach().clone()) for n, bf in module.named_buffers()
+                                           if bf.dtype == torch.float32 and bf.is_cuda and bf.is_contiguous() and bf.numel()]
+
+    # ------------------------------------------------------------------ EMA of the weights
+    @property
+    def ema_steps(self) -> int:
+        """Updates the average has counted (mmengine's ``steps``); ONE host read."""
+        return int(self.ema_state[1].item()) if self.ema_state is not None else 0
+
+    @property
+    def ema_iters(self) -> int:
+        return int(self.ema_state[2].item()) if self.ema_state is not None else 0
+
+    def set_ema_enabled(self, on: bool) -> None:
+        """``begin_epoch``: while off the average stays a copy of the weights; reaches the device with the next ``sync_ema()``."""
+        self._ema_want = bool(on)
+
+    def sync_ema(self) -> None:
+        """Push the ``enabled`` flag to ``ema_state``; a no-op while unchanged (and without EMA)."""
+        want = self._ema_want
+        if self.ema_state is not None and want != self._ema_enabled:
+            self.ema_state[3:4].copy_(torch.tensor([1.0 if want else 0.0], dtype=torch.float32))
+            self._ema_enabled = want
+
+    @torch.no_grad()
+    def swap_ema(self) -> None:
+        """Exchange masters and averages in place (+ the float buffers with ``update_buffers``); the working copies follow the masters.
+        Two calls restore every bit."""
+        if self.ema is None:
+            raise RuntimeError("swap_ema() needs FlatAdamW(ema=...)")
+        L, st = self._L, self._L.stream_ptr()
+        for b, e in zip(self.reducer.buckets, self.ema_bufs):
+            p, w, nw, n = b["mflat"], b["wflat"], b["n_work"], b["mflat"].numel()
+            if w is not None and nw:
+                L.call("dgtd_ema_swap", p.data_ptr(), e.data_ptr(), w.data_ptr(), self._w_dt, nw, st)
+            lo = nw if w is not None else 0
+            if n > lo:
+                L.call("dgtd_ema_swap", p.data_ptr() + 4 * lo, e.data_ptr() + 4 * lo, None, self._w_dt, n - lo, st)
+        for _, bf, e in self._ema_named_buffers:
+            L.call("dgtd_ema_swap", bf.data_ptr(), e.data_ptr(), None, self._w_dt, bf.numel(), st)
+
+    def ema_tensors(self) -> Dict[str, torch.Tensor]:
+        """The averages by state_dict key, in the parameters' logical shapes (views of the flat buffers; averaged buffers as they are)."""
+        out = {}
+        for b, e in zip(self.reducer.buckets, self.ema_bufs):
+            for i, name in enumerate(b["names"]):
+                out[name] = self._logical(b, i, e)
+        out.update({n: e for n, _, e in self._ema_named_buffers})
+        return out
+
+    @torch.no_grad()
+    def load_ema(self, named: Optional[dict], steps: int = 0, iters: int = 0) -> None:
+        """``named`` = averaged tensors by state_dict key (others are ignored), or ``None``: the average restarts as a copy of the weights."""
+        if self.ema is None:
+            raise RuntimeError("load_ema() needs FlatAdamW(ema=...)")
+        if named is None:
+            for b, e in zip(self.reducer.buckets, self.ema_bufs):
+                e.copy_(b["mflat"])
+            for _, bf, e in self._ema_named_buffers:
+                e.copy_(bf)
+        else:
+            for n, e in self.ema_tensors().items():
+                e.copy_(named[n])
+        self.ema_state[1:3].copy_(torch.tensor([float(steps), float(iters)], dtype=torch.float32))
+
+    def _ema_rest(self, bucket, runs, st) -> None:
+        """The EMA update over what this step's AdamW runs left out of ``bucket`` (slots without a gradient)."""
+        L, coef, pos = self._L, self.ema_state.data_ptr(), 0
+        p, e = bucket["mflat"], self.ema_bufs[bucket["index"]]
+        for lo, hi in [(r[0], r[1]) for r in runs] + [(p.numel(), p.numel())]:
+            if lo > pos:
+                L.call("dgtd_ema_flat", p.data_ptr() + 4 * pos, e.data_ptr() + 4 * pos, lo - pos, coef, st)
+            pos = max(pos, hi)
 
     @staticmethod
     def _norm_grid(n: int) -> int:
@@ -247,6 +470,10 @@ class FlatAdamW:
         bc1, bc2 = 1.0 - b1 ** self._steps, 1.0 - b2 ** self._steps
         st = L.stream_ptr()
         amp = self._state.data_ptr() if self._state is not None else None
+        es = self.ema_state.data_ptr() if self.ema is not None else None
+        if es is not None:                          # this step's coefficient, on the device, before anything reads it
+            L.call("dgtd_ema_schedule", es, self.ema["kind"], self.ema["momentum"], self.ema["gamma"], self.ema["interval"],
+                   self.ema["begin_iter"], st)
         if self.scaler is not None and not self._clip_norm:
             for b in self.reducer.buckets:          # GradScaler.unscale_'s found_inf over every (already all-reduced) gradient
                 if self.pipelined:
@@ -281,12 +508,21 @@ class FlatAdamW:
                         self._w_dt, hi - lo, float(self.param_groups[gi]["lr"]), b1, b2, self.eps,
                         float(self.param_groups[gi]["weight_decay"]), bc1, bc2, amp,
                         (lrp + 4 * gi) if lrp is not None else None)
-                if self.clip_grad is None:
+                if es is not None:
+                    L.call("dgtd_adamw_flat_ema", p.data_ptr() + 4 * lo, None if direct else (g.data_ptr() + 4 * lo),
+                           (g16.data_ptr() + 2 * lo) if direct else None, *tail, coef, self._clip_value,
+                           self.ema_bufs[i].data_ptr() + 4 * lo, es, st)
+                elif self.clip_grad is None:
                     L.call("dgtd_adamw_flat_g16" if direct else "dgtd_adamw_flat_amp", p.data_ptr() + 4 * lo,
                            (g16.data_ptr() + 2 * lo) if direct else (g.data_ptr() + 4 * lo), *tail, st)
                 else:
                     L.call("dgtd_adamw_flat_clip", p.data_ptr() + 4 * lo, None if direct else (g.data_ptr() + 4 * lo),
                            (g16.data_ptr() + 2 * lo) if direct else None, *tail, coef, self._clip_value, st)
+            if es is not None:
+                self._ema_rest(b, runs, st)
+        if es is not None:
+            for _, bf, e in self._ema_named_buffers:
+                L.call("dgtd_ema_flat", bf.data_ptr(), e.data_ptr(), bf.numel(), es, st)
         if self.scaler is not None:
             L.call("dgtd_loss_scale_update", self.scaler.state.data_ptr(), float(self.scaler.growth_factor),
                    float(self.scaler.backoff_factor), int(self.scaler.growth_interval), st)

@@ -405,6 +405,29 @@ int dgtd_adamw_flat_g16(float* p, const void* g16, float* m, float* v, void* w, 
 int dgtd_adamw_flat_clip(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr,
                          float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
                          const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, dgtd_stream s);
+/* ---- Exponential moving average of the weights (mmengine's EMAHook), on the device ----
+ * ema_state (device, fp32 [4]) = { coef of this step, steps (updates counted: mmengine's `steps`), iterations seen, enabled (written by
+ * the host, 1 = on) }.  dgtd_ema_schedule (one thread, once per optimizer step, before the AdamW launches) advances it:
+ *   enabled == 0 or iters < begin_iter : coef = 1 (the average is a copy of the weights), steps unchanged
+ *   steps == 0                         : coef = 1, steps = 1
+ *   steps % interval == 0              : coef = c(kind, steps), steps += 1
+ *   otherwise                          : coef = 0 (no update), steps += 1
+ * and iters += 1 in every case.  c: kind 0 (ExponentialMovingAverage) = momentum; kind 1 (MomentumAnnealingEMA) =
+ * max(momentum, gamma / (gamma + steps)); kind 2 (StochasticWeightAverage) = 1 / (steps / interval + 1), integer division.           */
+int dgtd_ema_schedule(float* ema_state, int kind, float momentum, float gamma, int interval, int begin_iter, dgtd_stream s);
+/* dgtd_adamw_flat_clip with the average updated in the same pass: ema fp32 [n] at the 16-byte phase of p, ema_coef_dev = &ema_state[0].
+ * After the AdamW update of an element: c == 0 leaves ema alone (neither read nor written), c == 1 sets e = p, otherwise
+ * e += c (p - e) with p the value just written.  On an overflowed step (amp_state[3] != 0) p, m, v, w stay as they are and the average
+ * is still updated against the unchanged p (the hook runs after every iteration).  ema == NULL: dgtd_adamw_flat_clip bit for bit.     */
+int dgtd_adamw_flat_ema(float* p, const float* g, const void* g16, float* m, float* v, void* w, dgtd_dtype w_dt, int64_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
+                        const float* amp_state, const float* lr_dev, const float* clip_coef_dev, float clip_value, float* ema,
+                        const float* ema_coef_dev, dgtd_stream s);
+/* The same update of the average without AdamW (stretches AdamW does not visit, float buffers): p, ema fp32 [n], 4-byte aligned.      */
+int dgtd_ema_flat(const float* p, float* ema, int64_t n, const float* ema_coef_dev, dgtd_stream s);
+/* Exchanges p and ema [n] in place (a captured graph holds their addresses); w (w_dt = DGTD_BF16 or DGTD_F16, at the phase of p and ema,
+ * or NULL) is rewritten from the new p.                                                                                              */
+int dgtd_ema_swap(float* p, float* ema, void* w, dgtd_dtype w_dt, int64_t n, dgtd_stream s);
 /* ---- Global gradient norm for clip_grad: partials per run, then one finalize ----
  * dgtd_grad_norm_partial: g [n] (dt = DGTD_F32, DGTD_BF16 or DGTD_F16, any element-aligned start) -> partial [grid] fp64, one value per
  * workgroup: kind 0 (L2) = sum of g^2 with every element widened to fp64 before it is squared (no overflow; non-finite iff an element
