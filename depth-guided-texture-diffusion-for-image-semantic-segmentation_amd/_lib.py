@@ -96,6 +96,8 @@ SIGNATURES = {
     "dgtd_ms_deform_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dgtd_preprocess_workspace": (_i64, [_i, _i, _i, _i]),
     "dgtd_preprocess": (_i, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dgtd_preprocess_batch_workspace": (_i64, [_vp, _i, _i]),
+    "dgtd_preprocess_batch": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _i64, _i, _vp]),
     "dgtd_prelu_fwd": (_i, [_vp, _fp, _vp, _i64, _i, _vp]),
     "dgtd_prelu_bwd": (_i, [_vp, _vp, _fp, _vp, _fp, _i64, _i, _vp]),
     "dgtd_ca_gate_fwd": (_i, [_vp, _vp, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _vp]),
@@ -221,3 +223,63 @@ def multi_copy(tensors, offsets, flat: torch.Tensor, to_tensors: bool = False) -
     P, I = C.c_void_p * n, C.c_int64 * n
     call("dgtd_multi_copy", P(*[t.data_ptr() for t in tensors]), I(*[int(o) for o in offsets]), I(*[t.numel() for t in tensors]), n, tdt,
          flat.data_ptr(), dtype_code(flat), int(to_tensors), stream_ptr())
+
+
+# ------------------------------------------------------------------------------------------------ dgtd_preprocess_batch job tables
+PREPROCESS_BATCH_MAX_JOBS = 65535       # DGTD_PREPROCESS_BATCH_MAX_JOBS: the job is the grid's second dimension
+PREPROCESS_MAX_SIDE = 1 << 24           # H and W of a plane (the entry's bound)
+OUT_INPUT, OUT_LABEL, OUT_DEPTH = 0, 1, 2
+
+
+class PreprocessJob(C.Structure):
+    """``dgtd_preprocess_job`` of include/dgtd.h (64 bytes, offsets only)."""
+    _fields_ = [("src_off", C.c_int64), ("mid_off", C.c_int64), ("tab_h_off", C.c_int64), ("tab_v_off", C.c_int64),
+                ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("flip", C.c_int32), ("normalize", C.c_int32),
+                ("out_sel", C.c_int32), ("batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+def _align16(v: int) -> int:
+    return (int(v) + 15) & ~15
+
+
+def resize_ksize(in_size: int, out_size: int) -> int:
+    """Taps per output index of Pillow's antialiased BILINEAR: ``2 * ceil(max(in / out, 1)) + 1`` (integer form, see preprocess_batch.hip)."""
+    return (1 if in_size <= out_size else -(-in_size // out_size)) * 2 + 1
+
+
+def preprocess_batch_layout(shapes, size: int) -> dict:
+    """Where every plane of a batch and its workspace regions go.  ``shapes``: one ``(H, W, C)`` per plane, in job order.  Pure host
+    arithmetic (no library call).  Planes are packed in order into one buffer, each at a 16-byte-aligned offset; the workspace holds
+    per job, in order, the uint8 intermediate ``[H][size][C]``, the horizontal table and the vertical table
+    (``size * (2 + ksize) * 4`` bytes each), every region rounded up to 16 bytes: the layout whose size
+    ``dgtd_preprocess_batch_workspace`` reports.  Returns ``{"src", "mid", "tab_h", "tab_v"}`` (lists of byte offsets) and
+    ``{"planes_bytes", "workspace_bytes"}``."""
+    S = int(size)
+    if S < 1:
+        raise DgtdError(f"preprocess_batch_layout: bad output size {size}")
+    if not 1 <= len(shapes) <= PREPROCESS_BATCH_MAX_JOBS:
+        raise DgtdError(f"preprocess_batch_layout: {len(shapes)} planes, a call takes 1..{PREPROCESS_BATCH_MAX_JOBS}")
+    out = {"src": [], "mid": [], "tab_h": [], "tab_v": []}
+    p = w = 0
+    for (H, W, Cc) in shapes:
+        if not (1 <= H <= PREPROCESS_MAX_SIDE and 1 <= W <= PREPROCESS_MAX_SIDE) or Cc not in (1, 3):
+            raise DgtdError(f"preprocess_batch_layout: bad plane shape {(H, W, Cc)}")
+        out["src"].append(p)
+        p += _align16(H * W * Cc)
+        out["mid"].append(w)
+        w += _align16(H * S * Cc)
+        out["tab_h"].append(w)
+        w += _align16(S * (2 + resize_ksize(W, S)) * 4)
+        out["tab_v"].append(w)
+        w += _align16(S * (2 + resize_ksize(H, S)) * 4)
+    out["planes_bytes"], out["workspace_bytes"] = p, w
+    return out
+
+
+def fill_preprocess_jobs(table, shapes, layout: dict, flips, normalizes, out_sels, batch_idx) -> None:
+    """Write one descriptor per plane into ``table`` (a ``PreprocessJob`` array, e.g. ``(PreprocessJob * n).from_buffer(pinned)``)."""
+    for j, (H, W, Cc) in enumerate(shapes):
+        jb = table[j]
+        jb.src_off, jb.mid_off, jb.tab_h_off, jb.tab_v_off = layout["src"][j], layout["mid"][j], layout["tab_h"][j], layout["tab_v"][j]
+        jb.H, jb.W, jb.C = int(H), int(W), int(Cc)
+        jb.flip, jb.normalize, jb.out_sel, jb.batch, jb.reserved = int(flips[j]), int(normalizes[j]), int(out_sels[j]), int(batch_idx[j]), 0

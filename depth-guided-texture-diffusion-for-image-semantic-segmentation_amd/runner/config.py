@@ -6,7 +6,8 @@ ignores, cod.py:38-46), ``optim_wrapper`` (AdamW, ``paramwise_cfg.custom_keys`` 
 (= fp16 autocast + dynamic loss scaling when the runner is built with ``compute_dtype=torch.float16``).  The external nest/mmengine runner is out of scope; this is what drives the HIP-backed model from
 the same file.  ``model:`` keys beyond ``type`` reach the model class as keyword arguments (``build_model``), so
 ``model: {type: cod, diffuser: {grid: 22, k: 5, max_step: 6}}`` selects a texture-diffuser configuration (keys ``grid``, ``k``, ``max_step``,
-``latent_dim``; an unknown key is a TypeError) with no further runner code.  Datasets need real data, so the loop is fed by any iterable of the dataset dict contract (runner/data.py)."""
+``latent_dim``; an unknown key is a TypeError) with no further runner code.  ``train_dataloader.dataset`` / ``val_dataloader.dataset`` bind through the same registry (runner/datasets.py: the reference's seven
+folder datasets) in ``Runner.fit`` / ``Runner.validate_config``; ``train`` / ``validate`` still take any iterable of the dataset dict contract (runner/data.py)."""
 from __future__ import annotations
 
 import math
@@ -17,7 +18,7 @@ import torch
 import yaml
 
 from .checkpoint import load_checkpoint_file, load_pretrained, save_checkpoint
-from .data import DefaultSampler, batches
+from .data import DefaultSampler, DeviceLoader, batches
 from .metrics import build_evaluators
 from .optim import EmaTorch, FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, parse_clip_grad, parse_ema
 
@@ -139,6 +140,7 @@ class Runner:
         self.sod_metrics = sod_metrics or (cfg.get("val_cfg") or {}).get("sod_metrics") or "skip"
         self.evaluators = build_evaluators(cfg.get("val_evaluator"), log, sod_metrics=self.sod_metrics)
         self.epoch = 0
+        self._device_loaders: Dict[tuple, DeviceLoader] = {}     # one per (dataset, split): staging buffers and decode threads persist over the epochs
         self._ema_gate()
 
     # ------------------------------------------------------------------ EMA of the weights
@@ -161,14 +163,84 @@ class Runner:
         return {k: avg[alias.get(k, k)] for k in self.model.state_dict() if alias.get(k, k) in avg}
 
     # ------------------------------------------------------------------ data
+    def build_dataset(self, split: str = "train"):
+        """``cfg['<split>_dataloader']['dataset']`` through the ``@export`` registry (runner/datasets.py holds the reference's seven
+        classes; ``SyntheticRGBD`` registers the same way).  An unknown ``type`` raises and lists the registered names."""
+        from .registry import build
+        block = (self.cfg.get(f"{split}_dataloader") or {}).get("dataset")
+        if not block or "type" not in block:
+            raise KeyError(f"the config has no {split}_dataloader.dataset block with a type")
+        ds = build(block)
+        if hasattr(ds, "decode"):
+            ds.seed = self.seed              # the flip coin is a function of (seed, epoch, index), the same on every rank
+        return ds
+
+    def model_img_size(self) -> Optional[int]:
+        """``model.img_size`` of the YAML, else the model's ``img_size`` attribute; None when neither says."""
+        v = (self.cfg.get("model") or {}).get("img_size", getattr(self.model, "img_size", None))
+        return None if v is None else int(v)
+
+    def check_dataset_size(self, dataset, split: str) -> None:
+        have, want = getattr(dataset, "image_size", getattr(dataset, "size", None)), self.model_img_size()
+        if have is not None and want is not None and int(have) != want:
+            raise ValueError(f"{split}_dataloader.dataset yields {have}x{have} images but model.img_size is {want}")
+
     def loader(self, dataset, split: str = "train", epoch: int = 0):
         """Batches of ``dataset`` the way the YAML's ``<split>_dataloader`` asks: batch_size, DefaultSampler(shuffle) partitioned
-        ``rank::world`` over a per-epoch seeded permutation."""
+        ``rank::world`` over a per-epoch seeded permutation.  A dataset with ``decode`` (runner/datasets.py) on the HIP device goes
+        through ``DeviceLoader`` (one upload and three launches per batch, ``num_workers`` decode threads, stacked fp32 tensors);
+        everything else through ``batches`` (lists of per-sample tensors from the dataset's own ``__getitem__``)."""
         dl = self.cfg.get(f"{split}_dataloader") or {}
         sc = dl.get("sampler") or {}
         sampler = DefaultSampler(len(dataset), shuffle=bool(sc.get("shuffle", split == "train")), seed=self.seed, rank=self.rank, world=self.world)
         sampler.set_epoch(epoch)
-        return batches(dataset, sampler, int(dl.get("batch_size", 1)), self.device)
+        if callable(getattr(dataset, "set_epoch", None)):
+            dataset.set_epoch(epoch)
+        batch_size, workers = int(dl.get("batch_size", 1)), int(dl.get("num_workers", 8))
+        if hasattr(dataset, "decode") and torch.device(self.device).type == "cuda":
+            # one loader per (dataset, split) over the epochs: its staging buffers and decode threads persist; ``close()`` ends them
+            key, made_with = (id(dataset), split), (batch_size, workers)
+            dev = self._device_loaders.get(key)
+            if dev is not None and (dev.dataset is not dataset or dev.made_with != made_with):     # the YAML block changed since
+                dev.close()
+                dev = None
+            if dev is None:
+                dev = self._device_loaders[key] = DeviceLoader(dataset, sampler, batch_size, self.device, torch.float32, workers)
+                dev.made_with = made_with
+            dev.sampler = sampler
+            return dev
+        return batches(dataset, sampler, batch_size, self.device)
+
+    def close(self) -> None:
+        """Stop the decode threads of every ``DeviceLoader`` that ``loader`` made and drop them (``fit`` and ``validate_config`` do
+        this when they return; a caller that drives ``train`` / ``validate`` with ``loader`` itself calls it when done)."""
+        for dev in self._device_loaders.values():
+            dev.close()
+        self._device_loaders.clear()
+
+    def fit(self):
+        """``script/train.sh``: build the train dataset (and the val dataset when ``val_interval`` is set) from the YAML and run
+        ``train`` over them.  A dataset whose size differs from the model's ``img_size`` raises before the first step."""
+        train_ds = self.build_dataset("train")
+        self.check_dataset_size(train_ds, "train")
+        val_ds = None
+        if self.val_interval and (self.cfg.get("val_dataloader") or {}).get("dataset"):
+            val_ds = self.build_dataset("val")
+            self.check_dataset_size(val_ds, "val")
+        try:
+            return self.train(lambda epoch: self.loader(train_ds, "train", epoch),
+                              val_loader_fn=None if val_ds is None else (lambda: self.loader(val_ds, "val")))
+        finally:
+            self.close()
+
+    def validate_config(self, split: str = "val") -> Dict[str, float]:
+        """``script/test.sh`` (``-m val``): build ``<split>_dataloader.dataset`` from the YAML and ``validate`` over it."""
+        ds = self.build_dataset(split)
+        self.check_dataset_size(ds, split)
+        try:
+            return self.validate(self.loader(ds, split))
+        finally:
+            self.close()
 
     # ------------------------------------------------------------------ train
     def train_step(self, batch: dict) -> torch.Tensor:

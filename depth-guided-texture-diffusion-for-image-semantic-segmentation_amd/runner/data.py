@@ -1,6 +1,7 @@
 """Synthetic RGB-D batches with the reference datasets' dict contract (twig/dataset/sod_train.py:55-83):
 {'raw': str, 'input': [3,S,S] ImageNet-normalised, 'label': [1,S,S] in {0,1}, 'depth': [1,S,S] in [0,1]},
-delivered as LISTS of per-sample tensors the way mmengine's pseudo_collate hands them to cod.forward."""
+delivered as LISTS of per-sample tensors the way mmengine's pseudo_collate hands them to cod.forward; the sampler; and the device
+input pipeline: per image (``device_preprocess``) and per batch of a folder dataset (``DeviceLoader``, stacked tensors)."""
 from __future__ import annotations
 
 import torch
@@ -131,3 +132,162 @@ def device_sample(rgb_u8: torch.Tensor, gt_u8: torch.Tensor, depth_u8: torch.Ten
     by re-seeding before each transform (:65-75)."""
     return {"input": device_preprocess(rgb_u8, size, True, flip, out_dtype), "label": device_preprocess(gt_u8, size, False, flip, out_dtype),
             "depth": device_preprocess(depth_u8, size, False, flip, out_dtype)}
+
+
+# ------------------------------------------------------------------------------------------------ batched device input pipeline
+class _StageSet:
+    """One pinned staging buffer ``[job table | planes]``, its device twin and a workspace, grown on demand (to a power of two of at
+    least 1 MiB, so the buffers settle after the first batches) and reused from batch to batch."""
+
+    def __init__(self, device):
+        self.device = device
+        self.pinned = self.dev = self.ws = None
+        self.uploaded = torch.cuda.Event()      # the upload has read the pinned buffer: the host may write the next batch into it
+        self.done = torch.cuda.Event()          # the three kernels have run: a consumer stream may read the outputs
+        self.busy = False
+        self.njobs = self.in_bytes = self.planes_bytes = 0
+
+    @staticmethod
+    def _capacity(n: int) -> int:
+        return max(1 << 20, 1 << (int(n) - 1).bit_length())
+
+    def pack(self, samples, size: int) -> None:
+        """Host side: descriptors and plane bytes of one batch into the pinned buffer.  ``samples``: ``(rgb, gt, depth, flip)`` per
+        sample as ``dataset.decode`` returns them."""
+        import ctypes
+        from .. import _lib as L
+        planes, flips, norm, sel, bidx = [], [], [], [], []
+        for b, (rgb, gt, dep, flip) in enumerate(samples):
+            for arr, s in ((rgb, L.OUT_INPUT), (gt, L.OUT_LABEL), (dep, L.OUT_DEPTH)):
+                planes.append(arr if arr.ndim == 3 else arr[:, :, None])
+                flips.append(bool(flip)), norm.append(s == L.OUT_INPUT), sel.append(s), bidx.append(b)
+        shapes = [p.shape for p in planes]
+        lay = L.preprocess_batch_layout(shapes, size)
+        table_bytes = len(planes) * ctypes.sizeof(L.PreprocessJob)
+        self.njobs, self.planes_bytes, self.ws_bytes = len(planes), lay["planes_bytes"], lay["workspace_bytes"]
+        self.table_bytes, self.in_bytes = table_bytes, table_bytes + lay["planes_bytes"]
+        if self.busy:
+            self.uploaded.synchronize()
+        if self.pinned is None or self.pinned.numel() < self.in_bytes:
+            self.pinned = torch.empty(self._capacity(self.in_bytes), dtype=torch.uint8, pin_memory=True)
+        host = self.pinned.numpy()
+        L.fill_preprocess_jobs((L.PreprocessJob * len(planes)).from_buffer(host), shapes, lay, flips, norm, sel, bidx)
+        for p, off in zip(planes, lay["src"]):
+            host[table_bytes + off: table_bytes + off + p.size] = p.reshape(-1)
+
+    def launch(self, batch: int, size: int, out_dtype: torch.dtype):
+        """Device side, on the current stream: ONE upload (table and planes together), then the three launches of
+        ``dgtd_preprocess_batch`` into fresh output tensors."""
+        import ctypes
+        from .. import _lib as L
+        if self.dev is None or self.dev.numel() < self.pinned.numel():
+            self.dev = torch.empty(self.pinned.numel(), dtype=torch.uint8, device=self.device)
+        if self.ws is None or self.ws.numel() < self.ws_bytes:
+            self.ws = torch.empty(self._capacity(self.ws_bytes), dtype=torch.uint8, device=self.device)
+        self.dev[:self.in_bytes].copy_(self.pinned[:self.in_bytes], non_blocking=True)
+        self.uploaded.record()
+        self.busy = True
+        out = [torch.empty(batch, c, size, size, dtype=out_dtype, device=self.device) for c in (3, 1, 1)]
+        mean, std = (ctypes.c_float * 3)(*IMAGENET_MEAN), (ctypes.c_float * 3)(*IMAGENET_STD)
+        L.call("dgtd_preprocess_batch", self.dev.data_ptr() + self.table_bytes, self.planes_bytes, self.dev.data_ptr(), self.pinned.data_ptr(),
+               self.njobs, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), batch, size, mean, std, self.ws.data_ptr(), self.ws.numel(),
+               L.dtype_code(out[0]), L.stream_ptr())
+        self.done.record()
+        return out
+
+
+class DeviceLoader:
+    """Batches of a folder dataset (``runner.datasets``: anything with ``decode(index, epoch)`` and ``image_size``) preprocessed on the
+    device: yields ``{'raw': [paths], 'input': Tensor[B,3,S,S], 'label': Tensor[B,1,S,S], 'depth': Tensor[B,1,S,S]}`` in
+    ``out_dtype``, bit-equal to the stacked host path ``dataset[i]``.  Per batch: the decodes run in a pool of
+    ``min(num_workers, 16)`` THREADS (never processes: a forked child of a process that holds the GPU is not safe), the decoded
+    planes and their job table go through one pinned staging buffer in ONE asynchronous copy, and ``dgtd_preprocess_batch`` writes the
+    three batch tensors in three launches; no per-sample tensors, no ``torch.stack``.
+
+    ``prefetch=True``: two staging sets alternate; the decodes of the next two batches are in flight and the upload and kernels of
+    batch k+1 are enqueued on a side stream BEFORE batch k is handed out, so they run while batch k trains.  (To enqueue them the
+    host waits for batch k+1's decodes first; the decode that overlaps with the training of batch k is batch k+2's, and the first
+    yield of an epoch waits for two batches of decode.)  An event orders the consumer's stream behind the preprocess of the batch
+    it receives.  ``prefetch=False``: everything on the current stream.
+
+    The yielded tensors are FRESH allocations per batch (only the staging sets are reused), so a consumer may keep them as long as it
+    likes.  ``sampler.epoch`` reaches ``decode`` (the flip coin); the last partial batch is yielded unless ``drop_last``."""
+
+    def __init__(self, dataset, sampler, batch_size: int, device="cuda", out_dtype: torch.dtype = torch.float32, num_workers: int = 8,
+                 prefetch: bool = True, drop_last: bool = False):
+        from concurrent.futures import ThreadPoolExecutor
+        from .. import _lib as L
+        if not callable(getattr(dataset, "decode", None)):
+            raise TypeError("DeviceLoader needs a dataset with decode(index, epoch) (runner.datasets); use batches(...) otherwise")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.DgtdError("DeviceLoader preprocesses on the HIP device; on CPU use batches(...) over the dataset's host path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.dataset, self.sampler, self.batch_size, self.out_dtype = dataset, sampler, int(batch_size), out_dtype
+        self.prefetch, self.drop_last, self.size = bool(prefetch), bool(drop_last), int(dataset.image_size)
+        self.num_threads = max(1, min(int(num_workers), 16))
+        self.pool = ThreadPoolExecutor(max_workers=self.num_threads, thread_name_prefix="dgtd-decode")
+        self.sets = [_StageSet(self.device), _StageSet(self.device)]
+        self.side = torch.cuda.Stream(self.device) if self.prefetch else None
+
+    def close(self) -> None:
+        """Stop the decode threads (pending decodes are dropped).  The loader is not usable afterwards."""
+        self.pool.shutdown(wait=True, cancel_futures=True)
+
+    def __del__(self):
+        pool = getattr(self, "pool", None)
+        if pool is not None:
+            pool.shutdown(wait=False, cancel_futures=True)
+
+    def __len__(self) -> int:
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _stage(self, k: int, indices, futures):
+        """Collect batch k's decodes, pack them and enqueue upload + preprocess (on the side stream when prefetching)."""
+        st = self.sets[k % 2]
+        st.pack([f.result() for f in futures], self.size)
+        with torch.cuda.device(self.device):
+            if self.side is not None:
+                with torch.cuda.stream(self.side):
+                    out = st.launch(len(indices), self.size, self.out_dtype)
+            else:
+                out = st.launch(len(indices), self.size, self.out_dtype)
+        return [self.dataset.images[i] for i in indices], out, st
+
+    def _hand_out(self, staged) -> dict:
+        raw, out, st = staged
+        if self.side is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(st.done)
+            for t in out:
+                t.record_stream(cur)        # allocated on the side stream, consumed on this one
+        return {"raw": raw, "input": out[0], "label": out[1], "depth": out[2]}
+
+    def __iter__(self):
+        epoch = int(getattr(self.sampler, "epoch", 0))
+        idx = list(self.sampler)
+        chunks = [idx[i:i + self.batch_size] for i in range(0, len(idx), self.batch_size)]
+        if chunks and self.drop_last and len(chunks[-1]) < self.batch_size:
+            chunks.pop()
+        decoding, submitted = [], 0
+
+        def fill():
+            nonlocal submitted
+            while submitted < len(chunks) and len(decoding) < (2 if self.prefetch else 1):
+                decoding.append((submitted, chunks[submitted], [self.pool.submit(self.dataset.decode, i, epoch) for i in chunks[submitted]]))
+                submitted += 1
+
+        fill()
+        staged = self._stage(*decoding.pop(0)) if decoding else None
+        while staged is not None:
+            fill()
+            cur = staged
+            if self.prefetch:
+                staged = self._stage(*decoding.pop(0)) if decoding else None
+                fill()
+                yield self._hand_out(cur)
+            else:
+                yield self._hand_out(cur)
+                staged = self._stage(*decoding.pop(0)) if decoding else None

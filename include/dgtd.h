@@ -497,6 +497,40 @@ int64_t dgtd_preprocess_workspace(int Hin, int Win, int C, int S);
 int dgtd_preprocess(const void* img_u8, void* out, const float* mean_host, const float* std_host, void* workspace, int Hin,
                     int Win, int C, int S, int flip, dgtd_dtype out_dt, dgtd_stream s);
 
+/* ---- The same pipeline for a whole batch of decoded images of differing sizes, in THREE launches whatever the batch size -------
+ * (coefficient tables of every plane and both axes; horizontal pass; vertical pass + ToTensor (+ Normalize)), writing the three
+ * batch tensors the model consumes in place: input [B,3,S,S], label [B,1,S,S], depth [B,1,S,S] in out_dt.  Same arithmetic as
+ * dgtd_preprocess, bit for bit.  A "plane" is one HWC uint8 image (C = 3 for RGB, 1 for GT / depth); all planes of the batch lie
+ * in ONE packed device buffer, each at a 16-byte-aligned offset, and one job descriptor per plane says where it is, what it is and
+ * where it goes.  Descriptors hold offsets only, never pointers, so the host can write descriptors and bytes into one pinned
+ * buffer and upload both with a single asynchronous copy.
+ *   jobs_dev  : the descriptor table on the device (what the kernels read; blockIdx.y indexes it, hence the bound below)
+ *   jobs_host : the same table readable by the host (what the entry validates and sizes its grids from)
+ * Workspace regions of a job: mid = uint8 intermediate [H][S][C]; tab_h / tab_v = per output index (start, count) int32 pairs
+ * [S][2] followed by the fixed-point weights int32 [S][ksize], ksize = 2 * max(ceil(in / S), 1) + 1 for in = W / H.  Regions of
+ * different jobs must not overlap (the entry checks alignment and bounds, not overlap).  dgtd_preprocess_batch_workspace returns
+ * the size of the canonical layout: jobs in order, each as mid, tab_h, tab_v, every region rounded up to 16 bytes (-1 on a bad
+ * job).  H and W of a plane: 1..2^24 each.  mean_host / std_host: HOST arrays of 3 floats for the jobs whose normalize flag is set (C = 3 only), or both NULL when no
+ * job normalizes.                                                                                                               */
+#define DGTD_PREPROCESS_BATCH_MAX_JOBS 65535
+typedef struct {
+  int64_t src_off;    /* byte offset of the plane in planes_u8 (16-byte aligned) */
+  int64_t mid_off;    /* workspace byte offsets (16-byte aligned): intermediate image, */
+  int64_t tab_h_off;  /*   horizontal coefficient table (from W), */
+  int64_t tab_v_off;  /*   vertical coefficient table (from H) */
+  int32_t H, W, C;
+  int32_t flip;       /* mirror the plane horizontally BEFORE the resize */
+  int32_t normalize;  /* (v/255 - mean[c]) / std[c] after ToTensor */
+  int32_t out_sel;    /* 0 = input (C = 3), 1 = label (C = 1), 2 = depth (C = 1) */
+  int32_t batch;      /* index into the batch dimension of that output */
+  int32_t reserved;   /* 0 */
+} dgtd_preprocess_job; /* 64 bytes */
+int64_t dgtd_preprocess_batch_workspace(const dgtd_preprocess_job* jobs_host, int njobs, int S);
+int dgtd_preprocess_batch(const void* planes_u8, int64_t planes_bytes, const dgtd_preprocess_job* jobs_dev,
+                          const dgtd_preprocess_job* jobs_host, int njobs, void* out_input, void* out_label, void* out_depth, int B,
+                          int S, const float* mean_host, const float* std_host, void* workspace, int64_t workspace_bytes,
+                          dgtd_dtype out_dt, dgtd_stream s);
+
 /* ---- Salient-object metrics of the validation loop: S-, E-, F-measure and MAE of py_sod_metrics 1.3.1 ---------------------
  * (as twig/metric/{S,E,F}measure.py and MAE.py call it; config/sod.yml:85-89, config/cod.yml:123-128).  pred [B,H,W] in pred_dt
  * (F32 / BF16 / F16, upcast exactly to fp32), gt [B,H,W] fp32, both quantised to uint8 as the wrappers do ((x * 255) truncated).
