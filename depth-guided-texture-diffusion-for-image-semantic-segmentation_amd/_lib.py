@@ -98,6 +98,8 @@ SIGNATURES = {
     "dgtd_preprocess": (_i, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dgtd_preprocess_batch_workspace": (_i64, [_vp, _i, _i]),
     "dgtd_preprocess_batch": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _i64, _i, _vp]),
+    "dgtd_predict_maps_workspace": (_i64, [_i]),
+    "dgtd_predict_maps": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _i, _vp, _i64, _vp]),
     "dgtd_prelu_fwd": (_i, [_vp, _fp, _vp, _i64, _i, _vp]),
     "dgtd_prelu_bwd": (_i, [_vp, _vp, _fp, _vp, _fp, _i64, _i, _vp]),
     "dgtd_ca_gate_fwd": (_i, [_vp, _vp, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _vp]),
@@ -283,3 +285,32 @@ def fill_preprocess_jobs(table, shapes, layout: dict, flips, normalizes, out_sel
         jb.src_off, jb.mid_off, jb.tab_h_off, jb.tab_v_off = layout["src"][j], layout["mid"][j], layout["tab_h"][j], layout["tab_v"][j]
         jb.H, jb.W, jb.C = int(H), int(W), int(Cc)
         jb.flip, jb.normalize, jb.out_sel, jb.batch, jb.reserved = int(flips[j]), int(normalizes[j]), int(out_sels[j]), int(batch_idx[j]), 0
+
+
+# ------------------------------------------------------------------------------------------------ dgtd_predict_maps job tables
+PREDICT_MAPS_MAX_JOBS = 65535           # DGTD_PREDICT_MAPS_MAX_JOBS: the job is the grid's second dimension
+PREDICT_MAX_SIDE = 1 << 24              # H and W of a map (the entry's bound)
+
+
+class PredictJob(C.Structure):
+    """``dgtd_predict_job`` of include/dgtd.h (32 bytes, offsets only)."""
+    _fields_ = [("out_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("batch", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+assert C.sizeof(PredictJob) == 32
+
+
+def predict_maps_layout(sizes):
+    """``(offsets, total_bytes)`` of the packed uint8 buffer ``dgtd_predict_maps`` fills: the maps in order, ``H * W`` bytes each, every
+    map at the next 16-byte-aligned offset; ``total_bytes`` ends with the last map (no padding behind it).  ``sizes``: one ``(H, W)``
+    per map.  Pure host arithmetic; the one place that computes this packing."""
+    if not 1 <= len(sizes) <= PREDICT_MAPS_MAX_JOBS:
+        raise DgtdError(f"predict_maps_layout: {len(sizes)} maps, a call takes 1..{PREDICT_MAPS_MAX_JOBS}")
+    offsets, end = [], 0
+    for (H, W) in sizes:
+        H, W = int(H), int(W)
+        if not (1 <= H <= PREDICT_MAX_SIDE and 1 <= W <= PREDICT_MAX_SIDE):
+            raise DgtdError(f"predict_maps_layout: bad map size {(H, W)}")
+        offsets.append(_align16(end))
+        end = offsets[-1] + H * W
+    return offsets, end

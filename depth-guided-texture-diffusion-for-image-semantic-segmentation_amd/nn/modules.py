@@ -825,7 +825,7 @@ def _stack(t):
 
 
 class cod(nn.Module):
-    """cod.py:36-224: ``forward(raw, input, label, depth, mode)`` with mode in {'loss', 'predict'}.
+    """cod.py:36-224: ``forward(raw, input, label, depth, mode)`` with mode in {'loss', 'predict', 'tensor'}.
 
     Extra keyword arguments (ignored by the reference, cod.py:38-46) are accepted and ignored.
     ``compute_dtype``: torch.float32 = exact-fp32 kernels (parity mode); torch.bfloat16 = bf16 MFMA
@@ -903,4 +903,6 @@ class cod(nn.Module):
         if mode == "predict":  # cod.py:152-153 + :219 (the PNG dumps of cod.py:156-217 are dropped)
             out = F.interpolate(P1[-1] + P2, size=label.shape[-2:], mode="bilinear", align_corners=False)
             return out.sigmoid(), label
+        if mode == "tensor":   # what cod.py:222 evidently meant to return: the logit map [B,1,S,S], no resize, no sigmoid (ops.predict_maps takes it)
+            return P1[-1] + P2
         raise NotImplementedError(f"Unsupported mode {mode}")

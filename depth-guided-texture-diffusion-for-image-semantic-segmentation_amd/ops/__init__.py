@@ -17,3 +17,4 @@ from .ms_deform_attn import MSDeformAttnFunction, ms_deform_attn  # noqa: F401
 from .conv_gemm import conv2d as conv2d_gemm, conv2d_tokens  # noqa: F401
 from .sod_metrics import SodMetrics, sod_metrics, sod_metrics_accumulate  # noqa: F401
 from .wfm import edt_nearest, weighted_fmeasure_accumulate, weighted_fmeasure_rows  # noqa: F401
+from .predict_maps import predict_maps  # noqa: F401

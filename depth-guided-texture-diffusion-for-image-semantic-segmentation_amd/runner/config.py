@@ -20,6 +20,7 @@ import yaml
 from .checkpoint import load_checkpoint_file, load_pretrained, save_checkpoint
 from .data import DefaultSampler, DeviceLoader, batches
 from .metrics import build_evaluators
+from .predict import MapWriter, parse_save_maps
 from .optim import EmaTorch, FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, parse_clip_grad, parse_ema
 
 MODEL_REGISTRY: Dict[str, Callable] = {}
@@ -94,6 +95,8 @@ class Runner:
         from ..dist import GradReducer, broadcast_parameters
         self.cfg, self.device, self.work_dir, self.log = cfg, device, work_dir, log
         self.rank, self.world, self.seed = rank, world, seed
+        # val_cfg.save_maps: the defaults of predict_config (out_dir, normalize); a misspelt key or value fails here, before the model is built
+        self.save_maps = parse_save_maps((cfg.get("val_cfg") or {}).get("save_maps"))
         self.model = build_model(cfg, compute_dtype).to(device)
         if any(h.get("type") == "our_init" for h in cfg.get("custom_hooks") or []):
             have = [p for p in ("pretrain/pvt_v2_b2.pth", "pretrain/convnext_base_22k_224.pth") if os.path.exists(p)]
@@ -185,11 +188,12 @@ class Runner:
         if have is not None and want is not None and int(have) != want:
             raise ValueError(f"{split}_dataloader.dataset yields {have}x{have} images but model.img_size is {want}")
 
-    def loader(self, dataset, split: str = "train", epoch: int = 0):
+    def loader(self, dataset, split: str = "train", epoch: int = 0, with_sizes: bool = False):
         """Batches of ``dataset`` the way the YAML's ``<split>_dataloader`` asks: batch_size, DefaultSampler(shuffle) partitioned
         ``rank::world`` over a per-epoch seeded permutation.  A dataset with ``decode`` (runner/datasets.py) on the HIP device goes
         through ``DeviceLoader`` (one upload and three launches per batch, ``num_workers`` decode threads, stacked fp32 tensors);
-        everything else through ``batches`` (lists of per-sample tensors from the dataset's own ``__getitem__``)."""
+        everything else through ``batches`` (lists of per-sample tensors from the dataset's own ``__getitem__``).  ``with_sizes``: the
+        ``DeviceLoader`` batches also carry each sample's original ``(H, W)`` under ``'size'`` (``predict`` writes maps at that size)."""
         dl = self.cfg.get(f"{split}_dataloader") or {}
         sc = dl.get("sampler") or {}
         sampler = DefaultSampler(len(dataset), shuffle=bool(sc.get("shuffle", split == "train")), seed=self.seed, rank=self.rank, world=self.world)
@@ -207,7 +211,7 @@ class Runner:
             if dev is None:
                 dev = self._device_loaders[key] = DeviceLoader(dataset, sampler, batch_size, self.device, torch.float32, workers)
                 dev.made_with = made_with
-            dev.sampler = sampler
+            dev.sampler, dev.with_sizes = sampler, bool(with_sizes)
             return dev
         return batches(dataset, sampler, batch_size, self.device)
 
@@ -316,6 +320,44 @@ class Runner:
         for ev in self.evaluators:
             metrics.update(ev.compute_metrics())
         return metrics
+
+    # ------------------------------------------------------------------ prediction maps (script/test.sh's PNG side effect)
+    @torch.no_grad()
+    def predict(self, loader: Iterable[dict], out_dir: str, minmax: bool = False) -> list:
+        """One grey-level PNG per sample of ``loader`` under ``out_dir``, named by the stem of ``raw``, at the sample's own size
+        (``batch['size']``, else the model's): ``cod.forward(mode='tensor')`` per batch -> ``runner.predict.MapWriter`` (one launch and
+        one device-to-host copy per batch, the encode overlapping the next forward).  Eval mode, and the averaged weights when EMAHook
+        is configured, exactly as ``validate``.  Returns the written paths, in order."""
+        was_training = self.model.training
+        self.model.eval()
+        if self.ema is not None:
+            self.swap_ema()
+        writer = MapWriter(out_dir, minmax=minmax)
+        try:
+            for batch in loader:
+                writer.submit(batch, self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="tensor"))
+        finally:
+            try:
+                paths = writer.close()
+            finally:
+                if self.ema is not None:
+                    self.swap_ema()
+                self.model.train(was_training)
+        return paths
+
+    def predict_config(self, split: str = "val", out_dir: Optional[str] = None, minmax: Optional[bool] = None) -> list:
+        """Build ``<split>_dataloader.dataset`` from the YAML and ``predict`` over it.  ``out_dir`` and ``minmax`` default to
+        ``val_cfg: {save_maps: {out_dir: ..., normalize: none | minmax}}``."""
+        defaults = self.save_maps or {"out_dir": None, "minmax": False}
+        out_dir = defaults["out_dir"] if out_dir is None else out_dir
+        if out_dir is None:
+            raise ValueError("predict_config needs out_dir, as an argument or as val_cfg.save_maps.out_dir")
+        ds = self.build_dataset(split)
+        self.check_dataset_size(ds, split)
+        try:
+            return self.predict(self.loader(ds, split, with_sizes=True), out_dir, defaults["minmax"] if minmax is None else bool(minmax))
+        finally:
+            self.close()
 
     # ------------------------------------------------------------------ checkpoint / resume
     def save(self, path: str) -> None:

@@ -211,10 +211,13 @@ class DeviceLoader:
     it receives.  ``prefetch=False``: everything on the current stream.
 
     The yielded tensors are FRESH allocations per batch (only the staging sets are reused), so a consumer may keep them as long as it
-    likes.  ``sampler.epoch`` reaches ``decode`` (the flip coin); the last partial batch is yielded unless ``drop_last``."""
+    likes.  ``sampler.epoch`` reaches ``decode`` (the flip coin); the last partial batch is yielded unless ``drop_last``.
+
+    ``with_sizes=True`` adds ``'size': [(H, W), ...]`` to the batch dict: the shape of each sample's decoded GT plane before the
+    resize, i.e. the resolution a prediction map is written at (``runner.predict.MapWriter``).  The default leaves the dict as it is."""
 
     def __init__(self, dataset, sampler, batch_size: int, device="cuda", out_dtype: torch.dtype = torch.float32, num_workers: int = 8,
-                 prefetch: bool = True, drop_last: bool = False):
+                 prefetch: bool = True, drop_last: bool = False, with_sizes: bool = False):
         from concurrent.futures import ThreadPoolExecutor
         from .. import _lib as L
         if not callable(getattr(dataset, "decode", None)):
@@ -226,6 +229,7 @@ class DeviceLoader:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.dataset, self.sampler, self.batch_size, self.out_dtype = dataset, sampler, int(batch_size), out_dtype
         self.prefetch, self.drop_last, self.size = bool(prefetch), bool(drop_last), int(dataset.image_size)
+        self.with_sizes = bool(with_sizes)
         self.num_threads = max(1, min(int(num_workers), 16))
         self.pool = ThreadPoolExecutor(max_workers=self.num_threads, thread_name_prefix="dgtd-decode")
         self.sets = [_StageSet(self.device), _StageSet(self.device)]
@@ -247,23 +251,27 @@ class DeviceLoader:
     def _stage(self, k: int, indices, futures):
         """Collect batch k's decodes, pack them and enqueue upload + preprocess (on the side stream when prefetching)."""
         st = self.sets[k % 2]
-        st.pack([f.result() for f in futures], self.size)
+        samples = [f.result() for f in futures]
+        st.pack(samples, self.size)
         with torch.cuda.device(self.device):
             if self.side is not None:
                 with torch.cuda.stream(self.side):
                     out = st.launch(len(indices), self.size, self.out_dtype)
             else:
                 out = st.launch(len(indices), self.size, self.out_dtype)
-        return [self.dataset.images[i] for i in indices], out, st
+        return [self.dataset.images[i] for i in indices], out, st, [tuple(int(v) for v in gt.shape[:2]) for (_, gt, _, _) in samples]
 
     def _hand_out(self, staged) -> dict:
-        raw, out, st = staged
+        raw, out, st, sizes = staged
         if self.side is not None:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(st.done)
             for t in out:
                 t.record_stream(cur)        # allocated on the side stream, consumed on this one
-        return {"raw": raw, "input": out[0], "label": out[1], "depth": out[2]}
+        batch = {"raw": raw, "input": out[0], "label": out[1], "depth": out[2]}
+        if self.with_sizes:
+            batch["size"] = sizes
+        return batch
 
     def __iter__(self):
         epoch = int(getattr(self.sampler, "epoch", 0))

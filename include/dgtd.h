@@ -531,6 +531,38 @@ int dgtd_preprocess_batch(const void* planes_u8, int64_t planes_bytes, const dgt
                           int S, const float* mean_host, const float* std_host, void* workspace, int64_t workspace_bytes,
                           dgtd_dtype out_dt, dgtd_stream s);
 
+/* ---- The output-side twin: prediction maps of a batch, each at its image's own size, packed as uint8 -----------------------------
+ * replaces the per-sample tail of predict mode's `_output.png` (twig/model/cod.py:156-217: output.sigmoid() through torchvision's
+ * save_image) after a resize to the original resolution: F.interpolate(bilinear, align_corners=False, no antialias) -> sigmoid ->
+ * mul(255) -> add(0.5) -> clamp(0, 255) -> uint8.  logits [B,S,S] in dt (F32 / BF16 / F16, upcast exactly to fp32; the model's
+ * P1[-1] + P2).  Job j fills out_u8[out_off .. out_off + H*W) row-major, one byte per pixel, from plane `batch` of the logits;
+ * bytes of out_u8 that no job covers (the alignment padding) are not written.  Descriptors hold offsets only, never pointers.
+ *   jobs_dev  : the descriptor table on the device (what the kernels read; blockIdx.y indexes it, hence the bound below)
+ *   jobs_host : the same table readable by the host (what the entry validates and sizes its grid from)
+ * fp32 throughout, every operation rounded, in this order: scale = in / out; src = max(scale * (dst + 0.5) - 0.5, 0); i0 = floor(src);
+ * i1 = i0 + (i0 < in - 1); l = src - i0; the two rows are blended horizontally first, then vertically; s = 1 / (1 + exp(-r)).
+ *   normalize = 0 : byte = floor(clamp(255 * s + 0.5, 0, 255)); a NaN gives 0; H = W = S is the identity resize.  ONE launch.
+ *   normalize = 1 : v = (s - min s) / (max s - min s + 1e-8) over the job's own H*W pixels, byte from v the same way; a constant map
+ *                   gives all 0.  THREE launches (clear the extrema, reduce, quantise by recomputing the resize).  min and max are
+ *                   integer atomics on the ordered bit pattern of s (no floating-point atomics): two calls give identical bytes.
+ *                   workspace: dgtd_predict_maps_workspace(njobs) bytes on the device (-1 for njobs outside 1..MAX_JOBS), 8-byte
+ *                   aligned; ignored (may be NULL) when normalize = 0.
+ * Refused with an error status before anything is launched: njobs outside 1..DGTD_PREDICT_MAPS_MAX_JOBS, an unknown dt or normalize,
+ * H or W outside 1..2^24, an out_off that is negative or not 16-byte aligned, a map that ends past out_bytes, a batch outside [0, B),
+ * a non-zero reserved field (maps of different jobs must not overlap; that is not checked).  No allocation, no synchronisation, no
+ * host read of device memory: legal inside stream capture.                                                                         */
+#define DGTD_PREDICT_MAPS_MAX_JOBS 65535
+typedef struct {
+  int64_t out_off;      /* byte offset of the map in out_u8 (16-byte aligned) */
+  int32_t H, W;         /* size of the map */
+  int32_t batch;        /* plane of the logits it is resized from */
+  int32_t reserved[3];  /* 0 */
+} dgtd_predict_job; /* 32 bytes */
+int64_t dgtd_predict_maps_workspace(int njobs);
+int dgtd_predict_maps(const void* logits, dgtd_dtype dt, int B, int S, const dgtd_predict_job* jobs_dev,
+                      const dgtd_predict_job* jobs_host, int njobs, void* out_u8, int64_t out_bytes, int normalize, void* workspace,
+                      int64_t workspace_bytes, dgtd_stream s);
+
 /* ---- Salient-object metrics of the validation loop: S-, E-, F-measure and MAE of py_sod_metrics 1.3.1 ---------------------
  * (as twig/metric/{S,E,F}measure.py and MAE.py call it; config/sod.yml:85-89, config/cod.yml:123-128).  pred [B,H,W] in pred_dt
  * (F32 / BF16 / F16, upcast exactly to fp32), gt [B,H,W] fp32, both quantised to uint8 as the wrappers do ((x * 255) truncated).
