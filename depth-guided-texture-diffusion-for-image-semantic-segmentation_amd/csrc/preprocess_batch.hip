@@ -1,13 +1,19 @@
-// preprocess_batch.hip — preprocess.hip's pipeline (RandomHorizontalFlip -> Resize((S,S)) -> ToTensor (-> Normalize)) for a whole
-// batch of decoded images of differing sizes in THREE launches, writing input [B,3,S,S], label [B,1,S,S] and depth [B,1,S,S] in
-// place.  One job descriptor per plane (include/dgtd.h: offsets only, never pointers); blockIdx.y is the job, blockIdx.x strides
-// over the job's elements, so a small plane simply retires most of its blocks at once.
-// Arithmetic: identical to preprocess.hip, bit for bit.  The coefficients are Pillow's (IEEE double, every operation rounds: this
-// file is compiled with contraction off), the two passes are int32 fixed-point sums whose order within a thread is the tap order of
-// the single-image kernels, and ToTensor/Normalize is (v/255 - mean)/std in float32.  Only the thread -> element map differs:
-// the horizontal pass gives a thread one (row, column, channel) with the channel fastest, so a wave's byte stores are contiguous;
-// the vertical pass gives a thread one (channel, row, column) with the column fastest, so the output stores are contiguous.
-// Byte work, HBM/latency-bound: sum(H*W*C) bytes in, 5*B*S*S elements out.
+// preprocess_batch.hip — the reference's input pipeline on the device (twig/dataset/sod_train.py:31-54, :65-83):
+// RandomHorizontalFlip -> Resize((S,S)) -> ToTensor (-> Normalize) for uint8 HWC planes already resident in HBM.  ONE pipeline, TWO
+// entries: dgtd_preprocess_batch takes a device table of job descriptors (include/dgtd.h: offsets only, never pointers) for a whole
+// batch of decoded images of differing sizes and writes input [B,3,S,S], label [B,1,S,S] and depth [B,1,S,S] in place;
+// dgtd_preprocess takes one image and builds its one job on the host.  Either way it is THREE launches: the coefficient tables of
+// both axes, the horizontal pass, the vertical pass with ToTensor (+ Normalize).  The three device bodies below take a job and the
+// base pointers; the batch kernels hand them jobs[blockIdx.y] (blockIdx.x strides over the job's elements, so a small plane simply
+// retires most of its blocks at once), the single-image kernels the job they received by value as a kernel argument.
+// Resize = Pillow's ImagingResample (BILINEAR, antialiased): triangle filter stretched by the down-scale factor, coefficients
+// normalised in double and converted to 22-bit fixed point, horizontal pass then vertical pass with a rounded uint8 intermediate.
+// Bit-exact against Pillow / the numpy restatement in oracle/preprocess_cpu.py: the coefficients are Pillow's (IEEE double, every
+// operation rounds: this file is compiled with contraction off), the two passes are int32 fixed-point sums in tap order, and
+// ToTensor/Normalize is (v/255 - mean)/std in float32, in that order.  Thread -> element map: the horizontal pass gives a thread one
+// (row, column, channel) with the channel fastest, so a wave's byte stores are contiguous; the vertical pass gives a thread one
+// (channel, row, column) with the column fastest, so the output stores are contiguous.
+// Byte work, HBM/latency-bound: sum(H*W*C) bytes in, C*S*S elements out per plane.
 #include "common.h"
 
 namespace {
@@ -20,10 +26,9 @@ __host__ __device__ __forceinline__ int ksize_for(int in_size, int out_size) {
   return (in_size <= out_size ? 1 : (in_size + out_size - 1) / out_size) * 2 + 1;
 }
 
-// tables of every job, both axes: thread t < 2S owns output index t % S of axis t / S (0: horizontal from W, 1: vertical from H)
-__global__ __launch_bounds__(256) void batch_coeffs_kernel(const dgtd_preprocess_job* __restrict__ jobs, char* __restrict__ ws, int S) {
+// tables of one job, both axes: thread t < 2S owns output index t % S of axis t / S (0: horizontal from W, 1: vertical from H)
+__device__ __forceinline__ void coeffs_body(const dgtd_preprocess_job& jb, char* __restrict__ ws, int S) {
 #pragma clang fp contract(off)
-  const dgtd_preprocess_job jb = jobs[blockIdx.y];
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= 2 * S) return;
   const int axis = t / S, xx = t - axis * S;
@@ -69,10 +74,8 @@ __device__ __forceinline__ int clip8(int acc) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// horizontal pass of every job: plane [H][W][C] -> mid [H][S][C]; the flip mirrors the INPUT columns (flip happens before the resize)
-__global__ __launch_bounds__(256) void batch_resize_h_kernel(const dgtd_preprocess_job* __restrict__ jobs, const uint8_t* __restrict__ planes,
-                                                             char* __restrict__ ws, int S) {
-  const dgtd_preprocess_job jb = jobs[blockIdx.y];
+// horizontal pass of one job: plane [H][W][C] -> mid [H][S][C]; the flip mirrors the INPUT columns (flip happens before the resize)
+__device__ __forceinline__ void resize_h_body(const dgtd_preprocess_job& jb, const uint8_t* __restrict__ planes, char* __restrict__ ws, int S) {
   const int H = jb.H, W = jb.W, C = jb.C, flip = jb.flip;
   const int ksize = ksize_for(W, S);
   const uint8_t* in = planes + jb.src_off;
@@ -96,15 +99,14 @@ __global__ __launch_bounds__(256) void batch_resize_h_kernel(const dgtd_preproce
   }
 }
 
-struct NormArgs { float mean[3], stdv[3]; };
+// four pairs: the single-image entry takes C up to 4; the batch entry (C = 3 only where it normalizes) fills the fourth with 0/1
+struct NormArgs { float mean[4], stdv[4]; };
 
-// vertical pass + ToTensor (+ Normalize) of every job: mid [H][S][C] -> out_sel[batch][C][S][S]
+// vertical pass + ToTensor (+ Normalize) of one job: mid [H][S][C] -> out_sel[batch][C][S][S]
 template <typename T>
-__global__ __launch_bounds__(256) void batch_resize_v_norm_kernel(const dgtd_preprocess_job* __restrict__ jobs, const char* __restrict__ ws,
-                                                                  T* __restrict__ out_input, T* __restrict__ out_label, T* __restrict__ out_depth,
-                                                                  int S, NormArgs na) {
+__device__ __forceinline__ void resize_v_norm_body(const dgtd_preprocess_job& jb, const char* __restrict__ ws, T* __restrict__ out_input,
+                                                   T* __restrict__ out_label, T* __restrict__ out_depth, int S, const NormArgs& na) {
 #pragma clang fp contract(off)
-  const dgtd_preprocess_job jb = jobs[blockIdx.y];
   const int C = jb.C;
   const int ksize = ksize_for(jb.H, S);
   const uint8_t* mid = (const uint8_t*)(ws + jb.mid_off);
@@ -121,21 +123,96 @@ __global__ __launch_bounds__(256) void batch_resize_v_norm_kernel(const dgtd_pre
     int acc = 1 << (PBITS - 1);
     for (int y = 0; y < cnt; ++y) acc += (int)mid[((size_t)(ymin + y) * S + xx) * C + c] * k[y];
     float t = (float)clip8(acc) / 255.0f;
-    if (jb.normalize) {
-      const float m = c == 0 ? na.mean[0] : (c == 1 ? na.mean[1] : na.mean[2]);
-      const float sd = c == 0 ? na.stdv[0] : (c == 1 ? na.stdv[1] : na.stdv[2]);
+    if (jb.normalize) {   // compare-and-select on the two bits of c < 4, not an index: a kernel-argument array indexed at run time
+                          // goes through scratch, and a chain of three c == k tests is compiled to branches instead of selects
+      const float m = (c & 1) ? ((c & 2) ? na.mean[3] : na.mean[1]) : ((c & 2) ? na.mean[2] : na.mean[0]);
+      const float sd = (c & 1) ? ((c & 2) ? na.stdv[3] : na.stdv[1]) : ((c & 2) ? na.stdv[2] : na.stdv[0]);
       t = (t - m) / sd;
     }
     out[i] = (T)t;   // i == (c * S + yy) * S + xx
   }
 }
 
+// batch entry: the job is the grid's second dimension and is read from the device table
+__global__ __launch_bounds__(256) void batch_coeffs_kernel(const dgtd_preprocess_job* __restrict__ jobs, char* __restrict__ ws, int S) {
+  const dgtd_preprocess_job jb = jobs[blockIdx.y];
+  coeffs_body(jb, ws, S);
+}
+__global__ __launch_bounds__(256) void batch_resize_h_kernel(const dgtd_preprocess_job* __restrict__ jobs, const uint8_t* __restrict__ planes,
+                                                             char* __restrict__ ws, int S) {
+  const dgtd_preprocess_job jb = jobs[blockIdx.y];
+  resize_h_body(jb, planes, ws, S);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void batch_resize_v_norm_kernel(const dgtd_preprocess_job* __restrict__ jobs, const char* __restrict__ ws,
+                                                                  T* __restrict__ out_input, T* __restrict__ out_label, T* __restrict__ out_depth,
+                                                                  int S, NormArgs na) {
+  const dgtd_preprocess_job jb = jobs[blockIdx.y];
+  resize_v_norm_body(jb, ws, out_input, out_label, out_depth, S, na);
+}
+
+// single-image entry: the one job is a kernel argument (64 bytes), so there is no table on the device and nothing to upload
+__global__ __launch_bounds__(256) void one_coeffs_kernel(dgtd_preprocess_job jb, char* __restrict__ ws, int S) { coeffs_body(jb, ws, S); }
+__global__ __launch_bounds__(256) void one_resize_h_kernel(dgtd_preprocess_job jb, const uint8_t* __restrict__ planes, char* __restrict__ ws, int S) {
+  resize_h_body(jb, planes, ws, S);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void one_resize_v_norm_kernel(dgtd_preprocess_job jb, const char* __restrict__ ws, T* __restrict__ out, int S, NormArgs na) {
+  resize_v_norm_body(jb, ws, out, (T*)nullptr, (T*)nullptr, S, na);
+}
+
 // a plane's sides are bounded so that every byte count below (H*W*C, H*S*C, the tables) stays far inside int64 and in + S inside int32
 constexpr int MAX_SIDE = 1 << 24;
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline int64_t table_bytes(int in_size, int S) { return (int64_t)S * (2 + ksize_for(in_size, S)) * 4; }
+// canonical workspace regions of one job, each rounded up to 16 bytes: mid, then tab_h, then tab_v
+inline int64_t mid_bytes(int H, int C, int S) { return align16((int64_t)H * S * C); }
+inline int64_t job_bytes(int H, int W, int C, int S) { return mid_bytes(H, C, S) + align16(table_bytes(W, S)) + align16(table_bytes(H, S)); }
+
+// blocks in x of the three launches: 2S table threads; the largest H*C rows of S; S*S outputs of at most max_c channels
+struct Grids { int coeffs, h, v; };
+inline Grids grids_for(int64_t max_hc, int max_c, int S) {
+  return {(int)cdiv(2 * (int64_t)S, 256), (int)std::min<int64_t>(cdiv(max_hc * S, 256), 1024),
+          (int)std::min<int64_t>(cdiv((int64_t)S * S * max_c, 256), 1024)};
+}
+
+NormArgs norm_args(const float* mean_host, const float* std_host, int C) {
+  NormArgs na;
+  for (int c = 0; c < 4; ++c) { na.mean[c] = (mean_host && c < C) ? mean_host[c] : 0.f; na.stdv[c] = (std_host && c < C) ? std_host[c] : 1.f; }
+  return na;
+}
 
 }  // namespace
+
+extern "C" int64_t dgtd_preprocess_workspace(int Hin, int Win, int C, int S) {
+  if (Hin < 1 || Win < 1 || S < 1 || C < 1 || C > 4) return -1;
+  return job_bytes(Hin, Win, C, S);
+}
+
+extern "C" int dgtd_preprocess(const void* img_u8, void* out, const float* mean_host, const float* std_host, void* workspace, int Hin,
+                               int Win, int C, int S, int flip, dgtd_dtype out_dt, dgtd_stream s) {
+  DGTD_PROF(s, DGTD_HBM, (double)Hin * Win * C + (double)dgtd_esize(out_dt) * C * S * S, "dgtd_preprocess[%dx%dx%d->%d]", Hin, Win, C, S);
+  DGTD_REQUIRE(Hin > 0 && Win > 0 && S > 0 && C >= 1 && C <= 4, "preprocess: bad sizes H=%d W=%d C=%d S=%d", Hin, Win, C, S);
+  DGTD_REQUIRE((mean_host == nullptr) == (std_host == nullptr), "preprocess: mean and std go together");
+  DGTD_REQUIRE(out_dt == DGTD_F32 || DGTD_IS_HALF(out_dt), "preprocess: bad output dtype %d", (int)out_dt);
+  hipStream_t st = (hipStream_t)s;
+  dgtd_preprocess_job jb = {};   // planes = img_u8, out_input = out: src_off, out_sel and batch are 0
+  jb.tab_h_off = mid_bytes(Hin, C, S);
+  jb.tab_v_off = jb.tab_h_off + align16(table_bytes(Win, S));
+  jb.H = Hin; jb.W = Win; jb.C = C;
+  jb.flip = flip;
+  jb.normalize = mean_host != nullptr;
+  const NormArgs na = norm_args(mean_host, std_host, C);
+  const Grids g = grids_for((int64_t)Hin * C, C, S);
+  char* ws = (char*)workspace;
+  hipLaunchKernelGGL(one_coeffs_kernel, dim3(g.coeffs), dim3(256), 0, st, jb, ws, S);
+  DGTD_CHECK_LAUNCH("preprocess_coeffs");
+  hipLaunchKernelGGL(one_resize_h_kernel, dim3(g.h), dim3(256), 0, st, jb, (const uint8_t*)img_u8, ws, S);
+  DGTD_CHECK_LAUNCH("preprocess_horizontal");
+  DGTD_DISPATCH(out_dt, hipLaunchKernelGGL(one_resize_v_norm_kernel<T_>, dim3(g.v), dim3(256), 0, st, jb, (const char*)ws, (T_*)out, S, na));
+  DGTD_CHECK_LAUNCH("preprocess_vertical");
+  return 0;
+}
 
 extern "C" int64_t dgtd_preprocess_batch_workspace(const dgtd_preprocess_job* jobs_host, int njobs, int S) {
   if (jobs_host == nullptr || njobs < 1 || S < 1) return -1;
@@ -143,7 +220,7 @@ extern "C" int64_t dgtd_preprocess_batch_workspace(const dgtd_preprocess_job* jo
   for (int j = 0; j < njobs; ++j) {
     const dgtd_preprocess_job& jb = jobs_host[j];
     if (jb.H < 1 || jb.W < 1 || jb.H > MAX_SIDE || jb.W > MAX_SIDE || (jb.C != 1 && jb.C != 3)) return -1;
-    total += align16((int64_t)jb.H * S * jb.C) + align16(table_bytes(jb.W, S)) + align16(table_bytes(jb.H, S));
+    total += job_bytes(jb.H, jb.W, jb.C, S);
   }
   return total;
 }
@@ -187,16 +264,14 @@ extern "C" int dgtd_preprocess_batch(const void* planes_u8, int64_t planes_bytes
   }
   DGTD_PROF(s, DGTD_HBM, bytes_in + (double)dgtd_esize(out_dt) * 5.0 * B * S * S, "dgtd_preprocess_batch[%dx->%d]", njobs, S);
   hipStream_t st = (hipStream_t)s;
-  NormArgs na;
-  for (int c = 0; c < 3; ++c) { na.mean[c] = mean_host ? mean_host[c] : 0.f; na.stdv[c] = std_host ? std_host[c] : 1.f; }
+  const NormArgs na = norm_args(mean_host, std_host, 3);
+  const Grids g = grids_for(max_h, 3, S);
   char* ws = (char*)workspace;
-  hipLaunchKernelGGL(batch_coeffs_kernel, dim3((int)cdiv(2 * (int64_t)S, 256), njobs), dim3(256), 0, st, jobs_dev, ws, S);
+  hipLaunchKernelGGL(batch_coeffs_kernel, dim3(g.coeffs, njobs), dim3(256), 0, st, jobs_dev, ws, S);
   DGTD_CHECK_LAUNCH("preprocess_batch_coeffs");
-  const int gh = (int)std::min<int64_t>(cdiv(max_h * S, 256), 1024);
-  hipLaunchKernelGGL(batch_resize_h_kernel, dim3(gh, njobs), dim3(256), 0, st, jobs_dev, (const uint8_t*)planes_u8, ws, S);
+  hipLaunchKernelGGL(batch_resize_h_kernel, dim3(g.h, njobs), dim3(256), 0, st, jobs_dev, (const uint8_t*)planes_u8, ws, S);
   DGTD_CHECK_LAUNCH("preprocess_batch_horizontal");
-  const int gv = (int)std::min<int64_t>(cdiv((int64_t)S * S * 3, 256), 1024);
-  DGTD_DISPATCH(out_dt, hipLaunchKernelGGL(batch_resize_v_norm_kernel<T_>, dim3(gv, njobs), dim3(256), 0, st, jobs_dev, (const char*)ws, (T_*)out_input,
+  DGTD_DISPATCH(out_dt, hipLaunchKernelGGL(batch_resize_v_norm_kernel<T_>, dim3(g.v, njobs), dim3(256), 0, st, jobs_dev, (const char*)ws, (T_*)out_input,
                                            (T_*)out_label, (T_*)out_depth, S, na));
   DGTD_CHECK_LAUNCH("preprocess_batch_vertical");
   return 0;

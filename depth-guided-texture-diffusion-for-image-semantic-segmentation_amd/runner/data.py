@@ -104,7 +104,7 @@ def device_preprocess(img_u8: torch.Tensor, size: int, normalize: bool = False, 
                       out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """One decoded image, uint8 [H, W, C] or [H, W] on the HIP device -> float [C, size, size]: the reference's per-sample transform
     chain RandomHorizontalFlip -> Resize((size, size)) (Pillow BILINEAR, antialiased) -> ToTensor (-> Normalize with the ImageNet
-    statistics) of twig/dataset/sod_train.py:31-54, bit-exact, as three small launches (csrc/preprocess.hip)."""
+    statistics) of twig/dataset/sod_train.py:31-54, bit-exact, as three small launches (csrc/preprocess_batch.hip)."""
     import ctypes
     from .. import _lib as L
     if img_u8.dtype != torch.uint8 or not img_u8.is_cuda:

@@ -487,20 +487,25 @@ int dgtd_ms_deform_attn_bwd(const void* value, const int64_t* spatial_shapes, co
                             void* grad_sampling_loc, void* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P,
                             dgtd_dtype dt, dgtd_stream s);
 
-/* ---- Input pipeline of one sample on the device --------------------------------------------------------
+/* ---- Input pipeline on the device: one pipeline, two entries ----------------------------------------------
  * replaces the per-sample transforms of twig/dataset/sod_train.py:31-54 (applied at :65-83): RandomHorizontalFlip (the caller
  * draws the coin) -> Resize((S,S)) = Pillow BILINEAR with antialiasing (requirements.txt:92, via torchvision Resize :148) ->
- * ToTensor -> optional Normalize.  img_u8 [Hin,Win,C] uint8 on the device (C = 3 RGB or 1 for GT / depth); out [C,S,S] in out_dt.
- * mean_host / std_host: HOST arrays of C floats or both NULL (no normalisation).  Bit-exact against Pillow + float32 ToTensor /
- * Normalize.  workspace: dgtd_preprocess_workspace(...) bytes on the device (uint8 intermediate + coefficient tables).           */
+ * ToTensor -> optional Normalize, bit-exact against Pillow + float32 ToTensor / Normalize.  Both entries run the same three device
+ * bodies (coefficient tables of both axes; horizontal pass; vertical pass + ToTensor (+ Normalize)) over job descriptors
+ * (dgtd_preprocess_job below), in THREE launches per call: dgtd_preprocess_batch reads a table of jobs on the device,
+ * dgtd_preprocess builds the one job of its image on the host and passes it as a kernel argument.
+ *
+ * One image: img_u8 [Hin,Win,C] uint8 on the device, C in 1..4 (3 RGB, 1 for GT / depth); out [C,S,S] in out_dt.
+ * mean_host / std_host: HOST arrays of C floats or both NULL (no normalisation).  workspace: dgtd_preprocess_workspace(...) bytes
+ * on the device, the canonical layout of that one job (mid, tab_h, tab_v as described below); -1 on bad sizes.                  */
 int64_t dgtd_preprocess_workspace(int Hin, int Win, int C, int S);
 int dgtd_preprocess(const void* img_u8, void* out, const float* mean_host, const float* std_host, void* workspace, int Hin,
                     int Win, int C, int S, int flip, dgtd_dtype out_dt, dgtd_stream s);
 
-/* ---- The same pipeline for a whole batch of decoded images of differing sizes, in THREE launches whatever the batch size -------
- * (coefficient tables of every plane and both axes; horizontal pass; vertical pass + ToTensor (+ Normalize)), writing the three
- * batch tensors the model consumes in place: input [B,3,S,S], label [B,1,S,S], depth [B,1,S,S] in out_dt.  Same arithmetic as
- * dgtd_preprocess, bit for bit.  A "plane" is one HWC uint8 image (C = 3 for RGB, 1 for GT / depth); all planes of the batch lie
+/* ---- The batch entry: decoded images of differing sizes, in THREE launches whatever the batch size ----------------------------
+ * writing the three batch tensors the model consumes in place: input [B,3,S,S], label [B,1,S,S], depth [B,1,S,S] in out_dt.  The
+ * device code is dgtd_preprocess's (one copy), so the two entries agree bit for bit; this one takes C = 1 or 3 only.
+ * A "plane" is one HWC uint8 image (C = 3 for RGB, 1 for GT / depth); all planes of the batch lie
  * in ONE packed device buffer, each at a 16-byte-aligned offset, and one job descriptor per plane says where it is, what it is and
  * where it goes.  Descriptors hold offsets only, never pointers, so the host can write descriptors and bytes into one pinned
  * buffer and upload both with a single asynchronous copy.

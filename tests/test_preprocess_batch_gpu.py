@@ -1,5 +1,6 @@
 """GPU: dgtd_preprocess_batch (csrc/preprocess_batch.hip) - a batch of planes of differing sizes in three launches - against the
-single-image entry (torch.equal per plane) and the numpy restatement of the transform chain, bit for bit."""
+single-image entry of the same file (torch.equal per plane: the job read from the device table and the job passed by value reach the
+same device code) and, as the independent check, the numpy restatement of the transform chain, bit for bit."""
 import ctypes
 
 import numpy as np

@@ -1,5 +1,6 @@
-// Stand-alone host check of the validation code of dgtd_preprocess_batch: the job table is an exactly-sized heap block and every call
-// is a refusal, so no launch is reached and no device is needed; an over-read of the table or a missed bound shows under the sanitizers.
+// Stand-alone host check of the validation code of dgtd_preprocess_batch and dgtd_preprocess: the job table is an exactly-sized heap
+// block and every call is a refusal, so no launch is reached and no device is needed; an over-read of the table or a missed bound shows
+// under the sanitizers.
 //   P=<package>/csrc; hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //       $P/preprocess_batch.hip $P/core.hip tools/preprocess_batch_hostcheck.cpp -o tools/_build/preprocess_batch_hostcheck && tools/_build/preprocess_batch_hostcheck
 #include <cstdio>
@@ -52,6 +53,22 @@ int main() {
   bad += expect(call(5, p, w), 2, "huge sides");  bad += dgtd_preprocess_batch_workspace(jobs, 5, S) != -1;  jobs[0].H = 97; jobs[0].W = 131;
   jobs[2].batch = 2;        bad += expect(call(5, p, w), 2, "batch index");      jobs[2].batch = 0;
   jobs[4].out_sel = 0;      bad += expect(call(5, p, w), 2, "C for output");     jobs[4].out_sel = 1;
+  free(jobs);
+  // the single-image entry: the same pipeline with its one job built on the host; every refusal comes before the first launch
+  auto one = [&](int C, int S1, const float* m, const float* sd, dgtd_dtype dt) {
+    return dgtd_preprocess(fake, fake, m, sd, fake, 97, 131, C, S1, 0, dt, nullptr);
+  };
+  bad += expect(one(0, S, nullptr, nullptr, DGTD_F32), 2, "single: C = 0");
+  bad += expect(one(5, S, nullptr, nullptr, DGTD_F32), 2, "single: C = 5");
+  bad += expect(one(3, 0, nullptr, nullptr, DGTD_F32), 2, "single: S = 0");
+  bad += expect(one(3, S, mean, nullptr, DGTD_F32), 2, "single: mean without std");
+  bad += expect(one(3, S, mean, stdv, DGTD_F64), 2, "single: bad dtype");
+  // its workspace is the one-job layout of the batch entry; bad sizes give -1 (no division by S = 0)
+  jobs = (dgtd_preprocess_job*)calloc(1, sizeof(dgtd_preprocess_job));
+  jobs[0].H = 97; jobs[0].W = 131; jobs[0].C = 3;
+  bad += dgtd_preprocess_workspace(97, 131, 3, S) != dgtd_preprocess_batch_workspace(jobs, 1, S);
+  bad += dgtd_preprocess_workspace(97, 131, 3, 0) != -1;
+  bad += dgtd_preprocess_workspace(97, 131, 5, S) != -1;
   free(jobs);
   printf(bad ? "FAILED %d\n" : "all refusals as expected\n", bad);
   return bad != 0;
