@@ -126,6 +126,7 @@ SIGNATURES = {
     "dgtd_batchnorm_bwd": (_i, [_vp, _vp, _fp, _fp, _vp, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "dgtd_sod_metrics_workspace": (_i64, [_i]),
     "dgtd_sod_metrics": (_i, [_vp, _i, _fp, _fp, _vp, _i, _i, _i, _vp]),
+    "dgtd_sod_metrics_ragged": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _fp, _vp, _vp]),
     "dgtd_sod_metrics_accumulate": (_i, [_fp, _i, _fp, _fp, _vp]),
     "dgtd_edt_nearest": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "dgtd_wfm_workspace": (_i64, [_i, _i, _i]),

@@ -143,14 +143,13 @@ __device__ __forceinline__ double s_object(double m, double sd) {
   return 2.0 * m / (((m * m + 1.0) + sd) + EPS);
 }
 
-__global__ __launch_bounds__(256) void sodm_finalize_kernel(void* ws, double* __restrict__ out, int H, int W) {
+// one image by one 256-thread block: the LUT, the moments and both curves from its stats and joint histogram into its row `o`
+__device__ __forceinline__ void finalize_image(const Stats st, const uint32_t* __restrict__ hist, double* __restrict__ o, int H, int W) {
 #pragma clang fp contract(off)
   __shared__ uint32_t fgh[256], bgh[256];
   __shared__ long long ired[4 * 8];
   __shared__ double dred[4 * 10];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const Stats st = *stats_of(ws, b);
-  const uint32_t* hist = hist_of(ws, b);
+  const int t = threadIdx.x;
   const long long N = (long long)H * W, cnt = st.cnt;
   fgh[t] = 0;
   bgh[t] = 0;
@@ -209,7 +208,6 @@ __global__ __launch_bounds__(256) void sodm_finalize_kernel(void* ws, double* __
   // curves: index i <-> threshold 255 - i (cumsum of the flipped histograms)
   long long tp = 0, fp = 0;
   for (int k = 255 - t; k < 256; ++k) { tp += fgh[k]; fp += bgh[k]; }
-  double* o = out + (size_t)b * ROW;
   {
     long long ps = tp + fp;
     if (ps == 0) ps = 1;
@@ -268,7 +266,159 @@ __global__ __launch_bounds__(256) void sodm_finalize_kernel(void* ws, double* __
   }
 }
 
-// state += this batch (images in order); slot = (sum sm / n, max(sum em / n), max(sum fm / n))
+__global__ __launch_bounds__(256) void sodm_finalize_kernel(void* ws, double* __restrict__ out, int H, int W) {
+  const int b = blockIdx.x;
+  finalize_image(*stats_of(ws, b), hist_of(ws, b), out + (size_t)b * ROW, H, W);
+}
+
+// ---- ragged uint8 input: image j is jobs[j].H x jobs[j].W bytes at jobs[j].out_off of pred8 and of gt8 (the packing of
+// dgtd_predict_maps: every map starts 16-byte aligned).  blockIdx.y is the job; a lane takes CHUNK = 16 consecutive pixels per step as
+// one dwordx4 of each buffer, the last N mod 16 pixels of a map byte by byte (bytes behind a map are never read).  (row, col) comes from
+// ONE 32-bit division per chunk (chunk starts are below 2^31) and is stepped from there.
+constexpr int CHUNK = 16;
+constexpr int RAGGED_MAX_BLOCKS = 32;     // blocks per job: 2 grid-stride steps of 256 lanes x 16 pixels each, up to this many
+
+// the chunk at pixel `base` of an N-pixel map: 16 bytes of each buffer as four words, and how many of them are pixels
+__device__ __forceinline__ int load_chunk(const uint8_t* __restrict__ p, const uint8_t* __restrict__ g, uint32_t base, int64_t N, uint32_t (&pw)[4],
+                                          uint32_t (&gw)[4]) {
+  if ((int64_t)base + CHUNK <= N) {
+    const uint4 a = *(const uint4*)(p + base), b = *(const uint4*)(g + base);
+    pw[0] = a.x; pw[1] = a.y; pw[2] = a.z; pw[3] = a.w;
+    gw[0] = b.x; gw[1] = b.y; gw[2] = b.z; gw[3] = b.w;
+    return CHUNK;
+  }
+  const int n = (int)(N - (int64_t)base);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { pw[q] = 0; gw[q] = 0; }
+#pragma unroll
+  for (int k = 0; k < CHUNK; ++k)
+    if (k < n) {
+      pw[k >> 2] |= (uint32_t)p[base + k] << (8 * (k & 3));
+      gw[k >> 2] |= (uint32_t)g[base + k] << (8 * (k & 3));
+    }
+  return n;
+}
+
+__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
+
+__global__ __launch_bounds__(256) void sodm_ragged_stats_kernel(const uint8_t* __restrict__ pred8, const uint8_t* __restrict__ gt8,
+                                                                const dgtd_predict_job* __restrict__ jobs, void* ws) {
+  const dgtd_predict_job jb = jobs[blockIdx.y];
+  const int W = jb.W;
+  const int64_t N = (int64_t)jb.H * W;
+  if ((int64_t)blockIdx.x * 256 * CHUNK >= N) return;                        // the whole block lies behind this job's image
+  __shared__ uint32_t s_inv_min[4], s_max[4], s_cnt[4];
+  __shared__ unsigned long long s_row[4], s_col[4];
+  const uint8_t* p = pred8 + jb.out_off;
+  const uint8_t* g = gt8 + jb.out_off;
+  const int64_t chunks = (N + CHUNK - 1) / CHUNK;
+  uint32_t inv_min = 0, mx = 0, cnt = 0;
+  unsigned long long srow = 0, scol = 0;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * 256) {
+    const uint32_t base = (uint32_t)(c * CHUNK);
+    uint32_t pw[4], gw[4];
+    const int n = load_chunk(p, g, base, N, pw, gw);
+    uint32_t row = base / (uint32_t)W, col = base - row * (uint32_t)W;
+#pragma unroll
+    for (int k = 0; k < CHUNK; ++k) {
+      if (k < n) {
+        const uint32_t v = byte_of(pw, k);
+        inv_min = max(inv_min, 255u - v);
+        mx = max(mx, v);
+        if (byte_of(gw, k) > 128u) {
+          ++cnt;
+          srow += row;
+          scol += col;
+        }
+      }
+      if (++col == (uint32_t)W) { col = 0; ++row; }
+    }
+  }
+  // integer reductions (order-free): xor butterfly per wave, the four waves through LDS, one set of global atomics per block
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    inv_min = max(inv_min, (uint32_t)__shfl_xor((int)inv_min, o, 64));
+    mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+    cnt += (uint32_t)__shfl_xor((int)cnt, o, 64);
+    srow += (unsigned long long)__shfl_xor((long long)srow, o, 64);
+    scol += (unsigned long long)__shfl_xor((long long)scol, o, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s_inv_min[w] = inv_min; s_max[w] = mx; s_cnt[w] = cnt; s_row[w] = srow; s_col[w] = scol; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k) {
+      inv_min = max(inv_min, s_inv_min[k]);
+      mx = max(mx, s_max[k]);
+      cnt += s_cnt[k];
+      srow += s_row[k];
+      scol += s_col[k];
+    }
+    Stats* st = stats_of(ws, blockIdx.y);
+    atomicMax(&st->inv_min, inv_min);
+    atomicMax(&st->max, mx);
+    if (cnt) { atomicAdd(&st->cnt, cnt); atomicAdd(&st->srow, srow); atomicAdd(&st->scol, scol); }
+  }
+}
+
+// Joint histogram.  Real saliency maps put most pixels into bins 0 and 255, so one LDS atomic per pixel into one histogram would
+// serialise on two addresses.  Two measures: a lane adds a RUN of equal (quadrant, G, p8) keys of its chunk with one atomic (a
+// saturated chunk costs one atomic instead of 16), and every wave owns a private copy of the histogram (4 x 8 KiB of LDS), so equal
+// keys of different waves never meet.  The copies are summed before the global atomics.
+__global__ __launch_bounds__(256) void sodm_ragged_hist_kernel(const uint8_t* __restrict__ pred8, const uint8_t* __restrict__ gt8,
+                                                               const dgtd_predict_job* __restrict__ jobs, void* ws) {
+  constexpr int BINS = 4 * 2 * 256;
+  const dgtd_predict_job jb = jobs[blockIdx.y];
+  const int W = jb.W;
+  const int64_t N = (int64_t)jb.H * W;
+  if ((int64_t)blockIdx.x * 256 * CHUNK >= N) return;
+  __shared__ uint32_t h[4 * BINS];
+  for (int i = threadIdx.x; i < 4 * BINS; i += 256) h[i] = 0;
+  int X, Y;
+  split_point(*stats_of(ws, blockIdx.y), &X, &Y);
+  __syncthreads();
+  uint32_t* mine = h + (threadIdx.x >> 6) * BINS;
+  const uint8_t* p = pred8 + jb.out_off;
+  const uint8_t* g = gt8 + jb.out_off;
+  const int64_t chunks = (N + CHUNK - 1) / CHUNK;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * 256) {
+    const uint32_t base = (uint32_t)(c * CHUNK);
+    uint32_t pw[4], gw[4];
+    const int n = load_chunk(p, g, base, N, pw, gw);
+    uint32_t row = base / (uint32_t)W, col = base - row * (uint32_t)W;
+    uint32_t run_key = 0, run = 0;
+#pragma unroll
+    for (int k = 0; k < CHUNK; ++k) {
+      if (k < n) {
+        const uint32_t q = ((int)row >= Y ? 2u : 0u) + ((int)col >= X ? 1u : 0u);
+        const uint32_t key = (q * 2u + (byte_of(gw, k) > 128u ? 1u : 0u)) * 256u + byte_of(pw, k);
+        if (key == run_key) {
+          ++run;
+        } else {
+          if (run) atomicAdd(&mine[run_key], run);
+          run_key = key;
+          run = 1;
+        }
+      }
+      if (++col == (uint32_t)W) { col = 0; ++row; }
+    }
+    if (run) atomicAdd(&mine[run_key], run);
+  }
+  __syncthreads();
+  uint32_t* gh = hist_of(ws, blockIdx.y);
+  for (int i = threadIdx.x; i < BINS; i += 256) {
+    const uint32_t v = ((h[i] + h[BINS + i]) + h[2 * BINS + i]) + h[3 * BINS + i];
+    if (v) atomicAdd(&gh[i], v);
+  }
+}
+
+__global__ __launch_bounds__(256) void sodm_ragged_finalize_kernel(const dgtd_predict_job* __restrict__ jobs, void* ws, double* __restrict__ out) {
+  const int b = blockIdx.x;
+  const dgtd_predict_job jb = jobs[b];
+  finalize_image(*stats_of(ws, b), hist_of(ws, b), out + (size_t)b * ROW, jb.H, jb.W);
+}
+
+// state += this batch (images in order); slot =(sum sm / n, max(sum em / n), max(sum fm / n))
 __global__ __launch_bounds__(256) void sodm_accumulate_kernel(const double* __restrict__ out, int B, double* __restrict__ state,
                                                               double* __restrict__ slot) {
 #pragma clang fp contract(off)
@@ -327,6 +477,44 @@ extern "C" int dgtd_sod_metrics(const void* pred, dgtd_dtype pred_dt, const floa
   DGTD_CHECK_LAUNCH("sodm_hist_kernel");
   hipLaunchKernelGGL(sodm_finalize_kernel, dim3(B), dim3(256), 0, st, workspace, out, H, W);
   DGTD_CHECK_LAUNCH("sodm_finalize_kernel");
+  return 0;
+}
+
+extern "C" int dgtd_sod_metrics_ragged(const uint8_t* pred8, const uint8_t* gt8, int64_t bytes, const dgtd_predict_job* jobs_dev,
+                                       const dgtd_predict_job* jobs_host, int njobs, double* out, void* workspace, dgtd_stream s) {
+  constexpr int MAX_SIDE = 1 << 24;
+  // the job is the grid's second dimension (gridDim.y <= 65535); checked before the table is read
+  DGTD_REQUIRE(njobs >= 1 && njobs <= DGTD_PREDICT_MAPS_MAX_JOBS, "sod_metrics_ragged: %d jobs, the grid's second dimension takes 1..%d", njobs,
+               DGTD_PREDICT_MAPS_MAX_JOBS);
+  DGTD_REQUIRE(pred8 != nullptr && gt8 != nullptr && jobs_dev != nullptr && jobs_host != nullptr && out != nullptr && workspace != nullptr,
+               "sod_metrics_ragged: null pointer");
+  DGTD_REQUIRE(((uintptr_t)pred8 & 15) == 0 && ((uintptr_t)gt8 & 15) == 0 && ((uintptr_t)jobs_dev & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
+               "sod_metrics_ragged: both byte buffers must be 16-byte aligned, the job table and the workspace 8-byte aligned");
+  double total = 0.0;
+  int64_t max_n = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const dgtd_predict_job& jb = jobs_host[j];
+    DGTD_REQUIRE(jb.H >= 1 && jb.W >= 1 && jb.H <= MAX_SIDE && jb.W <= MAX_SIDE, "sod_metrics_ragged: job %d: bad size H=%d W=%d (sides 1..%d)", j, jb.H,
+                 jb.W, MAX_SIDE);
+    const int64_t map = (int64_t)jb.H * jb.W;
+    DGTD_REQUIRE(map <= (int64_t)1 << 31, "sod_metrics_ragged: job %d: image of %dx%d pixels is too large", j, jb.H, jb.W);
+    DGTD_REQUIRE((jb.out_off & 15) == 0, "sod_metrics_ragged: job %d: offset %lld not 16-byte aligned", j, (long long)jb.out_off);
+    DGTD_REQUIRE(jb.out_off >= 0 && jb.out_off <= bytes - map, "sod_metrics_ragged: job %d: map [%lld,+%lld) outside the %lld bytes passed in", j,
+                 (long long)jb.out_off, (long long)map, (long long)bytes);
+    total += (double)map;
+    max_n = std::max(max_n, map);
+  }
+  DGTD_PROF(s, DGTD_HBM, 4.0 * total, "dgtd_sod_metrics_ragged[%d jobs]", njobs);
+  hipStream_t st = (hipStream_t)s;
+  if (hipMemsetAsync(workspace, 0, (size_t)njobs * WS_IMG, st) != hipSuccess) DGTD_FAIL(3, "sod_metrics_ragged: workspace memset failed");
+  const int64_t per_block = (int64_t)2 * 256 * CHUNK;
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(max_n, per_block), RAGGED_MAX_BLOCKS), (unsigned)njobs);
+  hipLaunchKernelGGL(sodm_ragged_stats_kernel, grid, dim3(256), 0, st, pred8, gt8, jobs_dev, workspace);
+  DGTD_CHECK_LAUNCH("sodm_ragged_stats_kernel");
+  hipLaunchKernelGGL(sodm_ragged_hist_kernel, grid, dim3(256), 0, st, pred8, gt8, jobs_dev, workspace);
+  DGTD_CHECK_LAUNCH("sodm_ragged_hist_kernel");
+  hipLaunchKernelGGL(sodm_ragged_finalize_kernel, dim3(njobs), dim3(256), 0, st, jobs_dev, workspace, out);
+  DGTD_CHECK_LAUNCH("sodm_ragged_finalize_kernel");
   return 0;
 }
 

@@ -16,5 +16,6 @@ from .loss import seg_loss, ssim_value  # noqa: F401
 from .ms_deform_attn import MSDeformAttnFunction, ms_deform_attn  # noqa: F401
 from .conv_gemm import conv2d as conv2d_gemm, conv2d_tokens  # noqa: F401
 from .sod_metrics import SodMetrics, sod_metrics, sod_metrics_accumulate  # noqa: F401
+from .sod_metrics import RaggedMaps, sod_metrics_ragged, sod_metrics_ragged_rows  # noqa: F401
 from .wfm import edt_nearest, weighted_fmeasure_accumulate, weighted_fmeasure_rows  # noqa: F401
 from .predict_maps import predict_maps  # noqa: F401

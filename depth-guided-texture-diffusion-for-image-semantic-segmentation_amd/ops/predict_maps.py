@@ -36,11 +36,32 @@ def _pinned_table(device: torch.device, nbytes: int, capturing: bool) -> Tuple[t
         ring["spare"] = torch.empty(max(4096, 1 << (nbytes - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
     slot = ring["slots"][ring["next"] % _RING]
     ring["next"] += 1
-    if slot.busy:
+    if slot.busy and not slot.uploaded.query():      # four calls later the upload has long run: the host waits only when it has not
         slot.uploaded.synchronize()
     if slot.pinned is None or slot.pinned.numel() < nbytes:
         slot.pinned = torch.empty(max(4096, 1 << (nbytes - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
     return slot.pinned, slot
+
+
+def upload_job_table(device: torch.device, sizes, offsets, batch_index) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(dev_table, pinned)``: the ``dgtd_predict_job`` table of ``sizes[j] = (H, W)`` at ``offsets[j]`` (plane ``batch_index[j]``) written
+    into a pinned table of the ring and sent to a fresh device tensor in ONE asynchronous copy on the current stream.  The entries read
+    ``dev_table`` on the device and ``pinned.data_ptr()`` on the host.  Shared by every op that takes this job table
+    (``predict_maps``, ``sod_metrics_ragged_rows``); legal while the stream captures after one eager call on the device."""
+    n = len(sizes)
+    nbytes = n * ctypes.sizeof(L.PredictJob)
+    pinned, slot = _pinned_table(device, nbytes, torch.cuda.is_current_stream_capturing())
+    table = (L.PredictJob * n).from_buffer(pinned.numpy())
+    for j, ((H, W), off, b) in enumerate(zip(sizes, offsets, batch_index)):
+        jb = table[j]
+        jb.out_off, jb.H, jb.W, jb.batch = off, H, W, b
+        jb.reserved[0] = jb.reserved[1] = jb.reserved[2] = 0
+    dev_table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    dev_table.copy_(pinned[:nbytes], non_blocking=True)
+    if slot is not None:
+        slot.uploaded.record()
+        slot.busy = True
+    return dev_table, pinned
 
 
 def predict_maps(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], batch_index: Optional[Sequence[int]] = None, minmax: bool = False,
@@ -71,18 +92,7 @@ def predict_maps(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], batch_i
         out = torch.empty(total, dtype=torch.uint8, device=logits.device)
     elif out.dtype != torch.uint8 or out.device != logits.device or not out.is_contiguous() or out.numel() < total:
         raise L.DgtdError(f"predict_maps: out must be a contiguous uint8 tensor of at least {total} bytes on {logits.device}")
-    nbytes = n * ctypes.sizeof(L.PredictJob)
-    pinned, slot = _pinned_table(logits.device, nbytes, torch.cuda.is_current_stream_capturing())
-    table = (L.PredictJob * n).from_buffer(pinned.numpy())
-    for j, ((H, W), off, b) in enumerate(zip(sizes, offsets, batch_index)):
-        jb = table[j]
-        jb.out_off, jb.H, jb.W, jb.batch = off, H, W, b
-        jb.reserved[0] = jb.reserved[1] = jb.reserved[2] = 0
-    dev_table = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
-    dev_table.copy_(pinned[:nbytes], non_blocking=True)
-    if slot is not None:
-        slot.uploaded.record()
-        slot.busy = True
+    dev_table, pinned = upload_job_table(logits.device, sizes, offsets, batch_index)
     ws = ws_bytes = None
     if minmax:
         ws_bytes = int(L.load().dgtd_predict_maps_workspace(n))

@@ -1,7 +1,7 @@
 """S-, E-, F-measure and MAE of py_sod_metrics 1.3.1 per image on the device (csrc/sod_metrics.hip, include/dgtd.h)."""
 from __future__ import annotations
 
-from typing import NamedTuple
+from typing import NamedTuple, Sequence, Tuple
 
 import torch
 
@@ -57,6 +57,45 @@ def sod_metrics(pred: torch.Tensor, gt: torch.Tensor) -> SodMetrics:
     [B,1,H,W] or [B,H,W], any H and W.  Both maps are quantised to uint8 the way the reference's wrappers do
     ((x * 255).astype(np.uint8), gt > 128)."""
     return split_rows(sod_metrics_rows(pred, gt))
+
+
+class RaggedMaps(NamedTuple):
+    """A batch of uint8 maps, each at its own size: map j is ``sizes[j] = (H, W)`` bytes at ``offsets[j]`` of ``pred8`` (the prediction
+    bytes, what ``ops.predict_maps`` returns) and at the same offset of ``gt8`` (the ground truth, foreground where the byte is above
+    128).  Both are flat uint8 device tensors in the packing of ``_lib.predict_maps_layout``; ``sizes`` and ``offsets`` live on the
+    host."""
+    pred8: torch.Tensor
+    gt8: torch.Tensor
+    sizes: Sequence[Tuple[int, int]]
+    offsets: Sequence[int]
+
+
+def sod_metrics_ragged_rows(maps: RaggedMaps) -> torch.Tensor:
+    """[n, ROW] fp64 rows (the layout of ``sod_metrics_rows``) of the ``n`` maps, each scored at its own size on its bytes as they are
+    (no quantisation on this path).  The job table goes up in one asynchronous copy from pinned memory (the ring of
+    ``ops.predict_maps``), then four launches on the current stream (workspace memset, stats, histogram, finalise); no
+    synchronisation, so the call can be captured in a graph after one eager call."""
+    from .predict_maps import upload_job_table
+    pred8, gt8 = maps.pred8, maps.gt8
+    L.check_cuda(pred8, gt8)
+    if pred8.dtype != torch.uint8 or gt8.dtype != torch.uint8 or pred8.ndim != 1 or gt8.ndim != 1 or gt8.device != pred8.device:
+        raise L.DgtdError("sod_metrics_ragged takes two flat uint8 tensors on one device")
+    sizes = [(int(h), int(w)) for (h, w) in maps.sizes]
+    offsets = [int(o) for o in maps.offsets]
+    n = len(sizes)
+    if len(offsets) != n or not 1 <= n <= L.PREDICT_MAPS_MAX_JOBS:
+        raise L.DgtdError(f"sod_metrics_ragged: {n} sizes and {len(offsets)} offsets, a call takes 1..{L.PREDICT_MAPS_MAX_JOBS} maps")
+    out = torch.empty(n, ROW, dtype=torch.float64, device=pred8.device)
+    ws = torch.empty(L.load().dgtd_sod_metrics_workspace(n), dtype=torch.uint8, device=pred8.device)
+    dev_table, pinned = upload_job_table(pred8.device, sizes, offsets, [0] * n)
+    L.call("dgtd_sod_metrics_ragged", L.ptr(pred8), L.ptr(gt8), min(pred8.numel(), gt8.numel()), L.ptr(dev_table), pinned.data_ptr(), n,
+           L.ptr(out), L.ptr(ws), L.stream_ptr())
+    return out
+
+
+def sod_metrics_ragged(maps: RaggedMaps) -> SodMetrics:
+    """Per-image metrics of a ragged batch of uint8 maps: what ``sod_metrics`` gives for each image alone at its own size."""
+    return split_rows(sod_metrics_ragged_rows(maps))
 
 
 def sod_metrics_accumulate(out: torch.Tensor, state: torch.Tensor, slot: torch.Tensor) -> None:

@@ -7,6 +7,6 @@ from .checkpoint import load_checkpoint, load_checkpoint_file, load_pretrained, 
 from .config import CosineByEpoch, Runner, build_model, build_optim, load_config  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
 from . import predict  # noqa: F401
-from .predict import MapWriter  # noqa: F401
+from .predict import MapWriter, score_maps  # noqa: F401
 from . import registry  # noqa: F401
 from .registry import build as build_exported, export, install_nest_shim, register_model  # noqa: F401

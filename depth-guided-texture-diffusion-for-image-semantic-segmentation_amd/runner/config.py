@@ -19,7 +19,7 @@ import yaml
 
 from .checkpoint import load_checkpoint_file, load_pretrained, save_checkpoint
 from .data import DefaultSampler, DeviceLoader, batches
-from .metrics import build_evaluators
+from .metrics import build_evaluators, check_score_size
 from .predict import MapWriter, parse_save_maps
 from .optim import EmaTorch, FlatAdamW, LossScaler, build_optimizer, clip_grad_torch, parse_clip_grad, parse_ema
 
@@ -91,12 +91,17 @@ class Runner:
     the configs' ``AmpOptimWrapper``.  On CPU (gloo tests of the host logic) it is torch.optim.AdamW over the same groups."""
 
     def __init__(self, cfg: dict, device="cuda", compute_dtype=torch.bfloat16, work_dir="work_dir", log: Callable = print,
-                 rank: int = 0, world: int = 1, seed: int = 0, sod_metrics: Optional[str] = None):
+                 rank: int = 0, world: int = 1, seed: int = 0, sod_metrics: Optional[str] = None, score_size: Optional[str] = None):
         from ..dist import GradReducer, broadcast_parameters
         self.cfg, self.device, self.work_dir, self.log = cfg, device, work_dir, log
         self.rank, self.world, self.seed = rank, world, seed
         # val_cfg.save_maps: the defaults of predict_config (out_dir, normalize); a misspelt key or value fails here, before the model is built
         self.save_maps = parse_save_maps((cfg.get("val_cfg") or {}).get("save_maps"))
+        # S/E/F-measure on the device (runner/sod_metrics.py) are opt-in: keyword, else val_cfg.sod_metrics, else "skip".  score_size:
+        # keyword, else val_cfg.score_size, else "network"; "original" scores the bytes of ops.predict_maps against the GT at each
+        # image's own size.  A bad value or combination fails here, before the model is built
+        self.sod_metrics = sod_metrics or (cfg.get("val_cfg") or {}).get("sod_metrics") or "skip"
+        self.score_size = check_score_size(score_size or (cfg.get("val_cfg") or {}).get("score_size"), self.sod_metrics, cfg.get("val_evaluator"))
         self.model = build_model(cfg, compute_dtype).to(device)
         if any(h.get("type") == "our_init" for h in cfg.get("custom_hooks") or []):
             have = [p for p in ("pretrain/pvt_v2_b2.pth", "pretrain/convnext_base_22k_224.pth") if os.path.exists(p)]
@@ -139,9 +144,7 @@ class Runner:
         hooks = cfg.get("default_hooks") or {}
         self.log_interval = int((hooks.get("logger") or {}).get("interval", 50))
         self.ckpt_interval = int((hooks.get("checkpoint") or {}).get("interval", 1))
-        # S/E/F-measure on the device (runner/sod_metrics.py) are opt-in: keyword, else val_cfg.sod_metrics, else "skip"
-        self.sod_metrics = sod_metrics or (cfg.get("val_cfg") or {}).get("sod_metrics") or "skip"
-        self.evaluators = build_evaluators(cfg.get("val_evaluator"), log, sod_metrics=self.sod_metrics)
+        self.evaluators = build_evaluators(cfg.get("val_evaluator"), log, sod_metrics=self.sod_metrics, score_size=self.score_size)
         self.epoch = 0
         self._device_loaders: Dict[tuple, DeviceLoader] = {}     # one per (dataset, split): staging buffers and decode threads persist over the epochs
         self._ema_gate()
@@ -188,12 +191,13 @@ class Runner:
         if have is not None and want is not None and int(have) != want:
             raise ValueError(f"{split}_dataloader.dataset yields {have}x{have} images but model.img_size is {want}")
 
-    def loader(self, dataset, split: str = "train", epoch: int = 0, with_sizes: bool = False):
+    def loader(self, dataset, split: str = "train", epoch: int = 0, with_sizes: bool = False, with_gt8: bool = False):
         """Batches of ``dataset`` the way the YAML's ``<split>_dataloader`` asks: batch_size, DefaultSampler(shuffle) partitioned
         ``rank::world`` over a per-epoch seeded permutation.  A dataset with ``decode`` (runner/datasets.py) on the HIP device goes
         through ``DeviceLoader`` (one upload and three launches per batch, ``num_workers`` decode threads, stacked fp32 tensors);
         everything else through ``batches`` (lists of per-sample tensors from the dataset's own ``__getitem__``).  ``with_sizes``: the
-        ``DeviceLoader`` batches also carry each sample's original ``(H, W)`` under ``'size'`` (``predict`` writes maps at that size)."""
+        ``DeviceLoader`` batches also carry each sample's original ``(H, W)`` under ``'size'`` (``predict`` writes maps at that size);
+        ``with_gt8``: also the packed GT planes at their own size under ``'gt8'`` (``score_size: original`` scores against them)."""
         dl = self.cfg.get(f"{split}_dataloader") or {}
         sc = dl.get("sampler") or {}
         sampler = DefaultSampler(len(dataset), shuffle=bool(sc.get("shuffle", split == "train")), seed=self.seed, rank=self.rank, world=self.world)
@@ -211,7 +215,8 @@ class Runner:
             if dev is None:
                 dev = self._device_loaders[key] = DeviceLoader(dataset, sampler, batch_size, self.device, torch.float32, workers)
                 dev.made_with = made_with
-            dev.sampler, dev.with_sizes = sampler, bool(with_sizes)
+            dev.sampler, dev.with_gt8 = sampler, bool(with_gt8)
+            dev.with_sizes = bool(with_sizes) or dev.with_gt8
             return dev
         return batches(dataset, sampler, batch_size, self.device)
 
@@ -238,13 +243,23 @@ class Runner:
             self.close()
 
     def validate_config(self, split: str = "val") -> Dict[str, float]:
-        """``script/test.sh`` (``-m val``): build ``<split>_dataloader.dataset`` from the YAML and ``validate`` over it."""
+        """``script/test.sh`` (``-m val``): build ``<split>_dataloader.dataset`` from the YAML and ``validate`` over it.  With
+        ``score_size: original`` the loader also delivers the GT planes at their own size, and when ``val_cfg.save_maps.out_dir`` is
+        set the same pass writes the scored bytes as PNGs there (one ``ops.predict_maps`` per batch serves both)."""
         ds = self.build_dataset(split)
         self.check_dataset_size(ds, split)
+        original = self.score_size == "original"
+        writer = None
+        if original and self.save_maps and self.save_maps["out_dir"] is not None:
+            writer = MapWriter(self.save_maps["out_dir"], minmax=self.save_maps["minmax"])
         try:
-            return self.validate(self.loader(ds, split))
+            return self.validate(self.loader(ds, split, with_gt8=original), writer=writer)
         finally:
-            self.close()
+            try:
+                if writer is not None:
+                    writer.close()
+            finally:
+                self.close()
 
     # ------------------------------------------------------------------ train
     def train_step(self, batch: dict) -> torch.Tensor:
@@ -295,9 +310,11 @@ class Runner:
 
     # ------------------------------------------------------------------ val (script/test.sh: `-m val`)
     @torch.no_grad()
-    def validate(self, loader: Iterable[dict]) -> Dict[str, float]:
+    def validate(self, loader: Iterable[dict], writer: Optional[MapWriter] = None) -> Dict[str, float]:
         """val_step = ``cod.forward(mode='predict')`` (cod.py:152-153, :219) per batch -> every evaluator's ``process`` ->
-        ``compute_metrics`` (mmengine ValLoop + Evaluator)."""
+        ``compute_metrics`` (mmengine ValLoop + Evaluator).  With ``score_size: original`` the step is ``cod.forward(mode='tensor')``
+        -> ``ops.predict_maps`` at ``batch['size']`` -> every evaluator's ``process(batch, ops.RaggedMaps)`` with ``batch['gt8']``: the
+        bytes a PNG would hold, against the GT at its own size; ``writer`` (a ``MapWriter``) then receives those same bytes."""
         was_training = self.model.training
         self.model.eval()
         for ev in self.evaluators:
@@ -309,7 +326,10 @@ class Runner:
             self.swap_ema()
         try:
             for batch in loader:
-                out = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="predict")
+                if self.score_size == "original":
+                    out = self._original_size_maps(batch, writer)
+                else:
+                    out = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="predict")
                 for ev in self.evaluators:
                     ev.process(batch, out)
         finally:
@@ -320,6 +340,18 @@ class Runner:
         for ev in self.evaluators:
             metrics.update(ev.compute_metrics())
         return metrics
+
+    def _original_size_maps(self, batch: dict, writer: Optional[MapWriter]):
+        from .. import ops
+        if not isinstance(batch, dict) or batch.get("gt8") is None or batch.get("size") is None:
+            raise ValueError("score_size: original needs batches with 'gt8' and 'size': build the loader with DeviceLoader(with_gt8=True) "
+                             "(Runner.loader(..., with_gt8=True))")
+        logits = self.model(batch.get("raw"), batch["input"], batch["label"], batch["depth"], mode="tensor")
+        sizes = [tuple(int(v) for v in hw) for hw in batch["size"]]
+        packed, offsets = ops.predict_maps(logits, sizes, minmax=bool(self.save_maps and self.save_maps["minmax"]))
+        if writer is not None:
+            writer.submit(batch, logits, packed=(packed, offsets))
+        return ops.RaggedMaps(packed, batch["gt8"], sizes, offsets)
 
     # ------------------------------------------------------------------ prediction maps (script/test.sh's PNG side effect)
     @torch.no_grad()

@@ -174,10 +174,14 @@ class _StageSet:
         L.fill_preprocess_jobs((L.PreprocessJob * len(planes)).from_buffer(host), shapes, lay, flips, norm, sel, bidx)
         for p, off in zip(planes, lay["src"]):
             host[table_bytes + off: table_bytes + off + p.size] = p.reshape(-1)
+        # where each sample's decoded GT plane (plane 3b + 1, one channel, as decoded: never flipped) lies in the staging buffer
+        self.gt_planes = [(table_bytes + lay["src"][3 * b + 1], planes[3 * b + 1].size) for b in range(len(samples))]
 
-    def launch(self, batch: int, size: int, out_dtype: torch.dtype):
+    def launch(self, batch: int, size: int, out_dtype: torch.dtype, gt8_layout=None):
         """Device side, on the current stream: ONE upload (table and planes together), then the three launches of
-        ``dgtd_preprocess_batch`` into fresh output tensors."""
+        ``dgtd_preprocess_batch`` into fresh output tensors.  ``gt8_layout = (offsets, total)``: a fourth fresh tensor, uint8
+        ``[total]``, receives every sample's GT plane at its offset, copied device to device out of the staging buffer (one small
+        copy per sample, no second upload), before ``done`` is recorded."""
         import ctypes
         from .. import _lib as L
         if self.dev is None or self.dev.numel() < self.pinned.numel():
@@ -192,6 +196,12 @@ class _StageSet:
         L.call("dgtd_preprocess_batch", self.dev.data_ptr() + self.table_bytes, self.planes_bytes, self.dev.data_ptr(), self.pinned.data_ptr(),
                self.njobs, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), batch, size, mean, std, self.ws.data_ptr(), self.ws.numel(),
                L.dtype_code(out[0]), L.stream_ptr())
+        if gt8_layout is not None:
+            offsets, total = gt8_layout
+            gt8 = torch.empty(total, dtype=torch.uint8, device=self.device)
+            for (src, n), off in zip(self.gt_planes, offsets):
+                gt8[off:off + n].copy_(self.dev[src:src + n], non_blocking=True)
+            out.append(gt8)
         self.done.record()
         return out
 
@@ -214,10 +224,15 @@ class DeviceLoader:
     likes.  ``sampler.epoch`` reaches ``decode`` (the flip coin); the last partial batch is yielded unless ``drop_last``.
 
     ``with_sizes=True`` adds ``'size': [(H, W), ...]`` to the batch dict: the shape of each sample's decoded GT plane before the
-    resize, i.e. the resolution a prediction map is written at (``runner.predict.MapWriter``).  The default leaves the dict as it is."""
+    resize, i.e. the resolution a prediction map is written at (``runner.predict.MapWriter``).  The default leaves the dict as it is.
+
+    ``with_gt8=True`` implies ``with_sizes`` and adds ``'gt8'``: a fresh uint8 device tensor per batch holding the decoded GT planes at
+    their own size (as decoded, never flipped), packed by ``_lib.predict_maps_layout(batch['size'])`` - the ground-truth half of
+    ``ops.RaggedMaps``.  It is filled from the staging buffer that is already on the device, on the stream the preprocess runs on, and
+    handed to the consumer's stream like the other outputs.  Without the flag the batch dict and the launches are what they are."""
 
     def __init__(self, dataset, sampler, batch_size: int, device="cuda", out_dtype: torch.dtype = torch.float32, num_workers: int = 8,
-                 prefetch: bool = True, drop_last: bool = False, with_sizes: bool = False):
+                 prefetch: bool = True, drop_last: bool = False, with_sizes: bool = False, with_gt8: bool = False):
         from concurrent.futures import ThreadPoolExecutor
         from .. import _lib as L
         if not callable(getattr(dataset, "decode", None)):
@@ -229,7 +244,8 @@ class DeviceLoader:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.dataset, self.sampler, self.batch_size, self.out_dtype = dataset, sampler, int(batch_size), out_dtype
         self.prefetch, self.drop_last, self.size = bool(prefetch), bool(drop_last), int(dataset.image_size)
-        self.with_sizes = bool(with_sizes)
+        self.with_gt8 = bool(with_gt8)
+        self.with_sizes = bool(with_sizes) or self.with_gt8
         self.num_threads = max(1, min(int(num_workers), 16))
         self.pool = ThreadPoolExecutor(max_workers=self.num_threads, thread_name_prefix="dgtd-decode")
         self.sets = [_StageSet(self.device), _StageSet(self.device)]
@@ -250,16 +266,19 @@ class DeviceLoader:
 
     def _stage(self, k: int, indices, futures):
         """Collect batch k's decodes, pack them and enqueue upload + preprocess (on the side stream when prefetching)."""
+        from .. import _lib as L
         st = self.sets[k % 2]
         samples = [f.result() for f in futures]
         st.pack(samples, self.size)
+        sizes = [tuple(int(v) for v in gt.shape[:2]) for (_, gt, _, _) in samples]
+        layout = L.predict_maps_layout(sizes) if self.with_gt8 else None
         with torch.cuda.device(self.device):
             if self.side is not None:
                 with torch.cuda.stream(self.side):
-                    out = st.launch(len(indices), self.size, self.out_dtype)
+                    out = st.launch(len(indices), self.size, self.out_dtype, layout)
             else:
-                out = st.launch(len(indices), self.size, self.out_dtype)
-        return [self.dataset.images[i] for i in indices], out, st, [tuple(int(v) for v in gt.shape[:2]) for (_, gt, _, _) in samples]
+                out = st.launch(len(indices), self.size, self.out_dtype, layout)
+        return [self.dataset.images[i] for i in indices], out, st, sizes
 
     def _hand_out(self, staged) -> dict:
         raw, out, st, sizes = staged
@@ -269,8 +288,10 @@ class DeviceLoader:
             for t in out:
                 t.record_stream(cur)        # allocated on the side stream, consumed on this one
         batch = {"raw": raw, "input": out[0], "label": out[1], "depth": out[2]}
-        if self.with_sizes:
+        if self.with_sizes or self.with_gt8:
             batch["size"] = sizes
+        if self.with_gt8:
+            batch["gt8"] = out[3]
         return batch
 
     def __iter__(self):

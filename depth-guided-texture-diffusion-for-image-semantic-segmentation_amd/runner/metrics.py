@@ -117,21 +117,48 @@ EVALUATORS = {"MAE": MAE, "meanIntersectionOverUnion": MeanIoU, "BinaryMIoU": Bi
 THIRD_PARTY = ("Emeasure", "Fmeasure", "Smeasure", "WeightedFmeasure")   # pure py_sod_metrics arithmetic: skipped with a message
 
 
-def build_evaluators(cfg_list, log=print, sod_metrics: str = "skip"):
+SCORE_SIZES = ("network", "original")
+NETWORK_SIZE_ONLY = ("meanIntersectionOverUnion", "BinaryMIoU", "WeightedFmeasure")
+
+
+def check_score_size(score_size, sod_metrics: str, cfg_list) -> str:
+    """``val_cfg.score_size``: ``network`` (the default: both maps at the network size) or ``original`` (the prediction bytes of
+    ``ops.predict_maps`` against the GT at each image's own size, through ``dgtd_sod_metrics_ragged``).  ``original`` needs
+    ``sod_metrics: device`` and refuses the evaluators that score at the network size only.  Raises ``ValueError``; returns the value."""
+    score_size = "network" if score_size is None else score_size
+    if score_size not in SCORE_SIZES:
+        raise ValueError(f"score_size must be one of {SCORE_SIZES}, got {score_size!r}")
+    if score_size == "original":
+        if sod_metrics != "device":
+            raise ValueError(f"score_size: original requires sod_metrics: device (the ragged metrics run on the device), got {sod_metrics!r}")
+        for item in cfg_list or []:
+            t = item.get("type") if isinstance(item, dict) else str(item)
+            if t in NETWORK_SIZE_ONLY:
+                raise ValueError(f"val_evaluator {t} scores at the network size only; it cannot be combined with score_size: original")
+    return score_size
+
+
+def build_evaluators(cfg_list, log=print, sod_metrics: str = "skip", score_size: str = "network"):
     """``val_evaluator`` entries by ``type``: this module's restated metrics first, then anything ``@export``-ed under that name
     (runner/registry.py: the reference's twig/metric classes register themselves there when they can be imported), then - with
     ``sod_metrics="device"`` - the device S/E/F-measure of runner/sod_metrics.py, which all share one accumulator (one kernel chain
     per batch), and the device WeightedFmeasure, which runs a chain of its own.  ``sod_metrics="skip"`` (the default) logs those
-    four as skipped."""
+    four as skipped.  ``score_size="original"`` (``check_score_size``): ``MAE`` is the device evaluator on the shared accumulator,
+    and every evaluator's ``process`` receives an ``ops.RaggedMaps``."""
     from . import registry
     from .sod_metrics import DEVICE_EVALUATORS, SodAccumulator
+    from .sod_metrics import MAE as DeviceMAE
     if sod_metrics not in ("skip", "device"):
         raise ValueError(f"sod_metrics must be 'skip' or 'device', got {sod_metrics!r}")
+    score_size = check_score_size(score_size, sod_metrics, cfg_list)
     out = []
     acc = None
     for item in cfg_list or []:
         t = item.get("type") if isinstance(item, dict) else str(item)
-        if t in EVALUATORS:
+        if score_size == "original" and t == "MAE":
+            acc = acc or SodAccumulator()
+            out.append(DeviceMAE(acc))
+        elif t in EVALUATORS:
             out.append(EVALUATORS[t]())
         elif t in registry.REGISTRY:
             out.append(registry.build(item if isinstance(item, dict) else {"type": t}))

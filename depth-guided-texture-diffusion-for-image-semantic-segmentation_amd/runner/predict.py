@@ -77,7 +77,7 @@ class MapWriter:
     logits (``cod.forward(mode='tensor')``), enqueues one device-to-host copy of the packed maps and an event, and returns without
     waiting for either; it then hands the PREVIOUS batch, whose copy has long landed, to ``workers`` encode THREADS (never
     processes), which run while the device computes the next forward.  A sample is written at ``batch['size'][i]``
-    (``DeviceLoader(with_sizes=True)``), or at the logits' own ``S x S`` when the batch has no sizes (synthetic data, datasets
+    (``DeviceLoader(with_sizes=True)``; ``submit(..., packed=...)`` takes maps that are already computed), or at the logits' own ``S x S`` when the batch has no sizes (synthetic data, datasets
     without ``decode``).  ``close()`` encodes what is left, joins the pool and re-raises the first encode error."""
 
     def __init__(self, out_dir: str, minmax: bool = False, workers: int = 8):
@@ -91,7 +91,9 @@ class MapWriter:
         self._seq = 0
 
     # -------------------------------------------------------------- device side
-    def submit(self, batch: dict, logits: torch.Tensor) -> None:
+    def submit(self, batch: dict, logits: torch.Tensor, packed=None) -> None:
+        """``packed = (bytes, offsets)``: the result of an ``ops.predict_maps`` call the caller has already made on these logits and
+        sizes (validation at the images' own size scores those bytes); the writer then skips its own call."""
         from .. import ops
         raws = list(batch["raw"])
         S = int(logits.shape[-1])
@@ -100,7 +102,7 @@ class MapWriter:
             raise ValueError(f"MapWriter.submit: {len(raws)} names, {len(sizes)} sizes, {logits.shape[0]} logit maps")
         st = self.stages[self.batches % 2]
         self._wait_encodes(st)                                   # the encodes of two batches ago read this buffer
-        packed, offsets = ops.predict_maps(logits, sizes, minmax=self.minmax)
+        packed, offsets = ops.predict_maps(logits, sizes, minmax=self.minmax) if packed is None else packed
         self._to_host(st.room(packed.numel()), packed)
         st.copied.record()
         st.jobs = [(map_path(self.out_dir, r), h, w, off) for r, (h, w), off in zip(raws, sizes, offsets)]
@@ -151,3 +153,80 @@ class MapWriter:
             if e is not None:
                 raise e
         return self.paths
+
+
+# ------------------------------------------------------------------------------------------------ scoring a folder of maps
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+
+
+def _by_stem(folder: str) -> dict:
+    return {os.path.splitext(f)[0]: os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith(IMAGE_EXTENSIONS)}
+
+
+def _same_size(pred_path: str, gt_path: str) -> None:
+    """Headers only: a map whose size differs from its ground truth's is refused before anything is scored."""
+    from PIL import Image
+    with Image.open(pred_path) as p, Image.open(gt_path) as g:
+        if p.size != g.size:
+            raise ValueError(f"{pred_path} is {p.size[1]}x{p.size[0]} but its ground truth {gt_path} is {g.size[1]}x{g.size[0]}: evaluation "
+                             "toolboxes resize the map here; this package scores each map at its own size and refuses")
+
+
+def _decode_pair(pred_path: str, gt_path: str):
+    import numpy as np
+    from PIL import Image
+    with Image.open(pred_path) as im:
+        p = np.asarray(im.convert("L"))
+    with Image.open(gt_path) as im:
+        g = np.asarray(im.convert("L"))
+    return p, g
+
+
+def score_maps(pred_dir: str, gt_dir: str, device="cuda", batch: int = 16, workers: int = 8) -> dict:
+    """Score a folder of grey-level prediction maps (from any source) against a folder of ground truths, each pair at its own size:
+    the ``summary()`` table of the device evaluators (Smeasure, MAE, adpEm, meanEm, maxEm, adpFm, meanFm, maxFm) over every GT of
+    ``gt_dir``.  Pairs are matched by file stem and scored in sorted order of the stems; the files are decoded in ``workers`` threads,
+    packed (``_lib.predict_maps_layout``), uploaded once per batch of ``batch`` pairs and scored by ``dgtd_sod_metrics_ragged``.  A GT
+    without a map raises ``FileNotFoundError`` listing the stems; a map whose size differs from its GT's raises ``ValueError``."""
+    from .. import _lib as L
+    from ..ops.sod_metrics import RaggedMaps
+    from .sod_metrics import SodAccumulator
+    preds, gts = _by_stem(os.fspath(pred_dir)), _by_stem(os.fspath(gt_dir))
+    missing = [s for s in sorted(gts) if s not in preds]
+    if missing:
+        raise FileNotFoundError(f"{pred_dir} has no map for {len(missing)} ground truth(s) of {gt_dir}: {', '.join(missing)}")
+    stems = sorted(gts)
+    if not stems:
+        raise FileNotFoundError(f"{gt_dir} holds no image files")
+    workers = max(1, min(int(workers), 16))
+    with ThreadPoolExecutor(max_workers=workers, thread_name_prefix="dgtd-score") as pool:
+        for f in [pool.submit(_same_size, preds[s], gts[s]) for s in stems]:
+            f.result()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.DgtdError("score_maps scores on the HIP device")
+    batch = max(1, min(int(batch), L.PREDICT_MAPS_MAX_JOBS))
+    acc = SodAccumulator()
+    pinned, uploaded = None, torch.cuda.Event()
+    with ThreadPoolExecutor(max_workers=workers, thread_name_prefix="dgtd-score") as pool, torch.cuda.device(device):
+        chunks = [stems[i:i + batch] for i in range(0, len(stems), batch)]
+        decoding = [pool.submit(_decode_pair, preds[s], gts[s]) for s in chunks[0]]
+        for k in range(len(chunks)):
+            pairs = [f.result() for f in decoding]
+            decoding = [pool.submit(_decode_pair, preds[s], gts[s]) for s in chunks[k + 1]] if k + 1 < len(chunks) else []
+            sizes = [p.shape for p, _ in pairs]
+            offsets, total = L.predict_maps_layout(sizes)
+            half = (total + 255) & ~255                          # [pred maps | gt maps]: ONE upload carries both halves
+            if k:
+                uploaded.synchronize()                           # the previous upload has read the pinned buffer
+            if pinned is None or pinned.numel() < 2 * half:
+                pinned = torch.empty(max(1 << 16, 1 << (2 * half - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
+            host = pinned.numpy()
+            for (p, g), off in zip(pairs, offsets):
+                host[off:off + p.size] = p.reshape(-1)
+                host[half + off:half + off + g.size] = g.reshape(-1)
+            dev = torch.empty(2 * half, dtype=torch.uint8, device=device)
+            dev.copy_(pinned[:2 * half], non_blocking=True)
+            uploaded.record()
+            acc.step(k, RaggedMaps(dev[:total], dev[half:half + total], sizes, offsets))
+    return acc.summary()

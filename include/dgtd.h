@@ -578,6 +578,24 @@ int dgtd_predict_maps(const void* logits, dgtd_dtype dt, int B, int S, const dgt
 int64_t dgtd_sod_metrics_workspace(int B);
 int dgtd_sod_metrics(const void* pred, dgtd_dtype pred_dt, const float* gt, double* out, void* workspace, int B, int H, int W,
                      dgtd_stream s);
+/* The same metrics of a RAGGED batch of uint8 maps, each image at its own size - the bytes dgtd_predict_maps writes (the bytes of the
+ * PNGs) against the ground truth at its own resolution.  Image j is H x W = jobs[j].H x jobs[j].W bytes, row-major, at byte offset
+ * jobs[j].out_off of pred8 and at the SAME offset of gt8 (the packing of dgtd_predict_maps: every map 16-byte aligned); jobs[j].batch
+ * and the reserved fields are ignored; bytes between the maps and behind the last one are never read.  Quantisation is already
+ * done: the prediction byte is p8, the ground truth is gt8 > 128.  Everything downstream - the split point, the joint [4][2][256]
+ * histogram, the finalise arithmetic, the row layout of out [njobs][DGTD_SODM_ROW] - is what dgtd_sod_metrics does, so a row equals
+ * bit for bit the row of dgtd_sod_metrics(B = 1) on float maps that quantise to the same bytes.
+ *   jobs_dev  : the descriptor table on the device (what the kernels read; blockIdx.y indexes it)
+ *   jobs_host : the same table readable by the host (what the entry validates and sizes its grid from)
+ * workspace: dgtd_sod_metrics_workspace(njobs) bytes, zeroed on `s` by the call itself.  THREE launches plus that memset: stats and
+ * histogram over (blocks, njobs), each block striding over its own job's pixels 16 bytes per lane (a block that starts behind its
+ * job's image leaves at once), then one finalise block per job.  Counts are integer atomics, fp64 runs in a fixed order: two calls on
+ * the same bytes are bit-identical, and a job's row does not depend on which other jobs share the call.
+ * Refused with an error status before anything is launched, `out` untouched: njobs outside 1..DGTD_PREDICT_MAPS_MAX_JOBS, a null
+ * pointer, pred8 or gt8 not 16-byte aligned, H or W outside 1..2^24, H*W > 2^31, an out_off that is negative or not 16-byte aligned,
+ * a map that ends past `bytes`.  No allocation, no synchronisation, no host read of device memory: legal inside stream capture.   */
+int dgtd_sod_metrics_ragged(const uint8_t* pred8, const uint8_t* gt8, int64_t bytes, const dgtd_predict_job* jobs_dev,
+                            const dgtd_predict_job* jobs_host, int njobs, double* out, void* workspace, dgtd_stream s);
 /* Running state of the wrappers' get_results() over every image seen: state [DGTD_SODM_STATE] fp64 (zeroed by the caller to
  * start) = { n, sum sm, sum mae, sum adp_em, sum adp_fm, 0, 0, 0, sum em_curve[256], sum fm_curve[256] }, images added in order.
  * running_slot [3] fp64 receives (sum sm / n, max(sum em_curve / n), max(sum fm_curve / n)) after this batch of B rows of `out`. */
