@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void ca_apply_fused_kernel(const T* __restrict
   if (tid < R) {
     float a = 0.f;
     for (int c = 0; c < C; ++c) a += w1[tid * C + c] * m[c];
-    a = fmaxf(a, 0.f);
+    a = a < 0.f ? 0.f : a;          // ReLU that keeps NaN (fmaxf maps it to 0)
     hdn[tid] = a;
     if (keeper) hidden[b * R + tid] = a;
   }

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void sam_apply_kernel(const T* __restrict__ xh
     const float* w = mlp ? v1 : w1;
     float a = 0.f;
     for (int cc = 0; cc < C; ++cc) a += w[j * C + cc] * m[zz * 128 + cc];
-    a = fmaxf(a, 0.f);
+    a = a < 0.f ? 0.f : a;          // ReLU that keeps NaN (fmaxf maps it to 0)
     hid[zz][mlp][j] = a;
     if (keeper) (mlp ? st.hw : st.hc)[((size_t)zz * B + b) * R + j] = a;
   }
