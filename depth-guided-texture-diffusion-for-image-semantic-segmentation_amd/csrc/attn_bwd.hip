@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ o
 #pragma unroll
     for (int j = 0; j < V; ++j) s += (float)a[j] * (float)g[j];
   }
-  s = group_sum(s, LPR);
+  s = group_sum<LPR>(s);
   if (item < total && sub == 0) {
     const int64_t b = bn / N, n = bn % N;
     delta[((size_t)b * heads + hd) * N + n] = s;

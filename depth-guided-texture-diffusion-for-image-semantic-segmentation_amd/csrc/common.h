@@ -76,21 +76,69 @@ __device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __
 // launch-geometry knobs (the tools/*_sweep.sh scripts drive them): read once, into a function-local `static const`
 static inline long env_int(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ---- lane reductions in registers ------------------------------------------------------------------------------------------------
+// Butterfly over lane ^ O with O a compile-time power of two.  Every step is a VALU instruction (DPP or a permlane swap), none is
+// an LDS round trip (__shfl_xor compiles to ds_bpermute_b32 + s_waitcnt lgkmcnt(0)):
+//   O = 1, 2  : DPP quad_perm [1,0,3,2] / [2,3,0,1]
+//   O = 4     : two bank-masked DPP row shifts (lanes 0-3, 8-11 of a row read lane + 4, lanes 4-7, 12-15 read lane - 4)
+//   O = 8     : DPP row_ror:8 (a rotation by half a 16-lane row is the exchange itself)
+//   O = 16, 32: v_permlane16_swap / v_permlane32_swap of a register with itself.  The swap exchanges the odd rows (upper half) of
+//               its first operand with the even rows (lower half) of its second, so of the two results one is the lane's own value
+//               and the other its partner's: which is which depends on the lane, and the commutative combine does not care.
+struct LaneAdd { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
+struct LaneMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+
+template <int CTRL, int BANK_MASK>
+__device__ __forceinline__ float dpp_move(float old, float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, 0xF, BANK_MASK, false));
+}
+// op(v, v of lane ^ O).  INV8 (O = 4 only): the caller guarantees v is the same in lanes l and l ^ 8, see group_reduce.
+template <int O, bool INV8 = false, typename Op>
+__device__ __forceinline__ float lane_xor_combine(float v, Op op) {
+  static_assert(O == 1 || O == 2 || O == 4 || O == 8 || O == 16 || O == 32, "lane_xor_combine: O must be a power of two below 64");
+  if constexpr (O == 1) return op(v, dpp_move<0xB1, 0xF>(v, v));
+  else if constexpr (O == 2) return op(v, dpp_move<0x4E, 0xF>(v, v));
+  else if constexpr (O == 4 && INV8) return op(v, dpp_move<0x124, 0xF>(v, v));                    // row_ror:4
+  else if constexpr (O == 4) return op(v, dpp_move<0x114, 0xA>(dpp_move<0x104, 0x5>(v, v), v));   // row_shl:4 | row_shr:4
+  else if constexpr (O == 8) return op(v, dpp_move<0x128, 0xF>(v, v));                            // row_ror:8
+  else {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto r = (O == 16) ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+  }
+}
+// N independent reductions across power-of-two groups of G adjacent lanes, step by step over all of them (N chains in flight
+// instead of one).  The tree is the one of a `for (o = G/2; o > 0; o >>= 1) v += shfl_xor(v, o)` loop: lane l pairs with l ^ o,
+// o from G/2 DOWN to 1, so a sum has the bits it had with shuffles.  The order matters for more than the bits: row_ror:4 hands lane
+// l the value of lane l - 4 (mod 16), which is lane l ^ 4 or lane (l ^ 4) ^ 8; it stands for the xor-4 exchange only because the
+// xor-8 step before it has made the values equal in lanes l and l ^ 8.  Do not reorder the steps; G = 8 has no such step before its
+// xor-4 and takes the exact form.
+template <int G, int N, typename Op>
+__device__ __forceinline__ void group_reduce(float (&v)[N], Op op) {
+  static_assert(G == 1 || G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "group_reduce: G must be a power of two <= 64");
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
+  for (int n = 0; n < N; ++n) if constexpr (G >= 64) v[n] = lane_xor_combine<32>(v[n], op);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
+  for (int n = 0; n < N; ++n) if constexpr (G >= 32) v[n] = lane_xor_combine<16>(v[n], op);
+#pragma unroll
+  for (int n = 0; n < N; ++n) if constexpr (G >= 16) v[n] = lane_xor_combine<8>(v[n], op);
+#pragma unroll
+  for (int n = 0; n < N; ++n) if constexpr (G >= 8) v[n] = lane_xor_combine<4, (G >= 16)>(v[n], op);
+#pragma unroll
+  for (int n = 0; n < N; ++n) if constexpr (G >= 4) v[n] = lane_xor_combine<2>(v[n], op);
+#pragma unroll
+  for (int n = 0; n < N; ++n) if constexpr (G >= 2) v[n] = lane_xor_combine<1>(v[n], op);
 }
-// reduce across a power-of-two sub-group of `g` adjacent lanes
-__device__ __forceinline__ float group_sum(float v, int g) {
-  for (int o = g >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+// v[n] += v[n] of lane ^ O for all n: one exact exchange step, for trees that do not run from G/2 down
+template <int O, int N> __device__ __forceinline__ void lane_xor_add(float (&v)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] = lane_xor_combine<O>(v[n], LaneAdd());
 }
+template <int G, int N> __device__ __forceinline__ void group_sum(float (&v)[N]) { group_reduce<G>(v, LaneAdd()); }
+// reduce across a power-of-two sub-group of G adjacent lanes; every lane of the group gets the result
+template <int G> __device__ __forceinline__ float group_sum(float v) { float a[1] = {v}; group_reduce<G>(a, LaneAdd()); return a[0]; }
+__device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
+__device__ __forceinline__ float wave_max(float v) { float a[1] = {v}; group_reduce<64>(a, LaneMax()); return a[0]; }
 
 // row index of accumulator register `reg` of a 32x32 MFMA result in lane half `h` (guide §3)
 __device__ __forceinline__ constexpr int mfma_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }

@@ -8,38 +8,55 @@
 // HBM traffic was already minimal.  Here a workgroup stages the input tile WITH its halo into LDS once (coalesced 16-B copies),
 // every lane keeps all K*K taps of its 2 channels in registers, and the inner loop is LDS reads + FMAs only.
 //   tile   : TY = 4 output rows (one per wave) x TXW = 16 output columns x 128 channels (64 lanes x 2)
-//   LDS    : (TY + K - 1) x (TXW + K - 1) x 128 bf16/fp32  (K = 7: 56 KB bf16)
+//   LDS    : (TY + K - 1) x (TXW + K - 1) x 128 bf16/fp32, rounded up to 4 KB  (K = 7: 56 KB bf16)
 #include "common.h"
 
 namespace {
 
 constexpr int TY = 4, TXW = 16, TXS = 8;   // TXS = strip of outputs a lane computes at a time
 
-// stage rows [y0 - P, y0 + TY + P) x cols [x0 - P, x0 + TXW + P) x channels [cb*128, +128) of image b into LDS, zero padded.
-// All of a thread's 16-byte loads are issued before the first LDS store (fully unrolled, registers), so the tile arrives with
-// one round trip of latency instead of one per chunk.
+// The 16-byte global loads that bring rows [y0 - P, y0 + TY + P) x cols [x0 - P, x0 + TXW + P) x channels [cb*128, +128) of image b
+// to a workgroup, zero padded, and their LDS stores.  load() only issues: a position outside the image (and the slots past the
+// tile's end) reads a clamped, always-valid address and its value is dropped by a select in store(), and the LDS tile is rounded
+// up to whole 256-thread passes (SLOTS), so neither a load nor a store stands under control flow and no wait separates the loads.  The kernel issues its other global loads between the two calls:
+// everything a workgroup needs from memory arrives with one round trip of latency.
 template <typename T, int K>
-__device__ __forceinline__ void stage_tile(T* __restrict__ tile, const T* __restrict__ x, int b, int y0, int x0, int cb, int H, int W,
-                                           int C, int tid) {
+struct TileStage {
   typedef typename Vec16<T>::type VT;
-  constexpr int V = Vec16<T>::N, P = K / 2, RW = TXW + K - 1, RH = TY + K - 1, CPP = 128 / V;   // 16-B chunks per position
-  constexpr int TOTAL = RH * RW * CPP, NCH = (TOTAL + 255) / 256;
+  static constexpr int V = Vec16<T>::N, P = K / 2, RW = TXW + K - 1, RH = TY + K - 1, CPP = 128 / V;   // 16-B chunks per position
+  static constexpr int TOTAL = RH * RW * CPP, NCH = (TOTAL + 255) / 256, SLOTS = NCH * 256;
   VT v[NCH];
+  bool ok[NCH];
+  __device__ __forceinline__ void load(const T* __restrict__ x, int b, int y0, int x0, int cb, int H, int W, int C, int tid) {
 #pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int i = tid + k * 256;
-    const int ch = i % CPP, pos = i / CPP, xx = pos % RW, yy = pos / RW;
-    const int gy = y0 + yy - P, gx = x0 + xx - P;
-    if (i < TOTAL && gy >= 0 && gy < H && gx >= 0 && gx < W) v[k] = *reinterpret_cast<const VT*>(x + (((size_t)b * H + gy) * W + gx) * C + cb * 128 + ch * V);
-    else
-#pragma unroll
-      for (int j = 0; j < V; ++j) v[k][j] = (T)0.f;
+    for (int k = 0; k < NCH; ++k) {
+      const int i = tid + k * 256;
+      const int ch = i % CPP, pos = i / CPP, xx = pos % RW, yy = pos / RW;
+      const int gy = y0 + yy - P, gx = x0 + xx - P;
+      ok[k] = i < TOTAL && gy >= 0 && gy < H && gx >= 0 && gx < W;
+      const int cy = min(max(gy, 0), H - 1), cx = min(max(gx, 0), W - 1);
+      v[k] = *reinterpret_cast<const VT*>(x + (((size_t)b * H + cy) * W + cx) * C + cb * 128 + ch * V);
+    }
   }
+  __device__ __forceinline__ void store(T* __restrict__ tile, int tid) const {
 #pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    const int i = tid + k * 256;
-    if (i < TOTAL) *reinterpret_cast<VT*>(tile + (size_t)i * V) = v[k];   // pos * 128 + ch * V == i * V
+    for (int k = 0; k < NCH; ++k) {
+      const int i = tid + k * 256;
+      VT o;
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = ok[k] ? v[k][j] : (T)0.f;
+      *reinterpret_cast<VT*>(tile + (size_t)i * V) = o;   // pos * 128 + ch * V == i * V; the slots past TOTAL are LDS slack
+    }
   }
+};
+
+// the value of a 4- or 8-byte register operand is computed (and a load behind it complete) at this point of the program: an empty
+// asm the optimiser can neither look through nor move a producer across
+template <typename P>
+__device__ __forceinline__ void pin_here(P& v) {
+  static_assert(sizeof(P) == 4 || sizeof(P) == 8, "pin_here: one or two registers");
+  if constexpr (sizeof(P) == 4) { unsigned u = __builtin_bit_cast(unsigned, v); asm volatile("" : "+v"(u)); v = __builtin_bit_cast(P, u); }
+  else { unsigned long long u = __builtin_bit_cast(unsigned long long, v); asm volatile("" : "+v"(u)); v = __builtin_bit_cast(P, u); }
 }
 
 // MODE 0: y = conv + bias   MODE 1: y = gelu(conv + bias)   MODE 2: y = aux * gelu'(conv + bias)   MODE 3: y = conv + bias + aux
@@ -61,18 +78,36 @@ __global__ __launch_bounds__(256) void dwconv_tiled_fwd_kernel(const T* __restri
   const int tx = t % txn;
   const int b = t / txn;
   const int y0 = ty * TY, x0 = tx * TXW, c0 = cb * 128 + lane * 2;
-  stage_tile<T, K>(tile, x, b, y0, x0, cb, H, W, C, tid);
-  // all K*K taps of this lane's two channels, and the bias, stay in registers (loaded behind the tile: the staging registers are dead)
+  TileStage<T, K> st;
+  st.load(x, b, y0, x0, cb, H, W, C, tid);
+  // all K*K taps of this lane's two channels, and the bias, stay in registers
   // the lane's two channels travel as float2 values: the multiply-adds compile to v_pk_fma_f32 (two FMAs per VALU instruction)
   typedef float f2 __attribute__((ext_vector_type(2)));
   f2 w[K * K];
 #pragma unroll
   for (int i = 0; i < K * K; ++i) { w[i][0] = wt[(size_t)i * C + c0]; w[i][1] = wt[(size_t)i * C + c0 + 1]; }
+  const float* bp = bias ? bias : wt;      // no bias: a valid address, the value is dropped
+  const float b0 = bp[c0], b1 = bp[c0 + 1];
   f2 bv;
-  bv[0] = bias ? bias[c0] : 0.f; bv[1] = bias ? bias[c0 + 1] : 0.f;
-  __syncthreads();
+  bv[0] = bias ? b0 : 0.f; bv[1] = bias ? b1 : 0.f;
   const int oy = y0 + wave;                       // this wave's output row
-  if (oy >= H) return;
+  // modes 2 and 3: the aux values of the wave's outputs, first and second strip, in the same round trip (outputs past the image's
+  // edge read a clamped address: no load under a branch)
+  static_assert(TXW == 2 * TXS, "the aux prefetch holds two strips");
+  PT ax[TXS], ax_next[TXS];
+  if (MODE >= 2) {
+    const size_t arow = ((size_t)b * H + min(oy, H - 1)) * W;
+#pragma unroll
+    for (int i = 0; i < TXS; ++i) {
+      ax[i] = *reinterpret_cast<const PT*>(aux + (arow + min(x0 + i, W - 1)) * C + c0);
+      ax_next[i] = *reinterpret_cast<const PT*>(aux + (arow + min(x0 + TXS + i, W - 1)) * C + c0);
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);              // every global load above is issued before the first LDS store waits for one
+  st.store(tile, tid);
+  __syncthreads();
+  // a wave whose row lies past the image's end runs on (its LDS rows exist) and stores nothing: an early exit here would be a
+  // block for the compiler to sink the tap loads into, behind the barrier
 #pragma unroll 1
   for (int s = 0; s < TXW / TXS; ++s) {
     const int sx = s * TXS;
@@ -94,19 +129,24 @@ __global__ __launch_bounds__(256) void dwconv_tiled_fwd_kernel(const T* __restri
 #pragma unroll
         for (int i = 0; i < TXS; ++i) acc[i] = __builtin_elementwise_fma(in[i + kx], w[ky * K + kx], acc[i]);
     }
+    // the sums are complete HERE.  Without this the compiler sinks each output's 49 multiply-adds into the `ox < W` block of its
+    // store: eight dependent chains one after another, with all 7 x 14 staged inputs of the strip held in registers for them.
+    // The same holds for an aux load, which would start its round trip only there.
+#pragma unroll
+    for (int i = 0; i < TXS; ++i) { pin_here(acc[i]); if (MODE >= 2) pin_here(ax[i]); }
 #pragma unroll
     for (int i = 0; i < TXS; ++i) {
       const int ox = x0 + sx + i;
-      if (ox < W) {
+      if (ox < W && oy < H) {
         const size_t o = (((size_t)b * H + oy) * W + ox) * C + c0;
         PT r;
         if (MODE == 2) {
-          PT g = *reinterpret_cast<const PT*>(aux + o);
+          const PT g = ax[i];
           r[0] = (T)((float)g[0] * gelu_grad_fast(acc[i][0])); r[1] = (T)((float)g[1] * gelu_grad_fast(acc[i][1]));
         } else if (MODE == 1) {
           r[0] = (T)gelu_fast(acc[i][0]); r[1] = (T)gelu_fast(acc[i][1]);
         } else if (MODE == 3) {
-          PT g = *reinterpret_cast<const PT*>(aux + o);
+          const PT g = ax[i];
           r[0] = (T)(acc[i][0] + (float)g[0]); r[1] = (T)(acc[i][1] + (float)g[1]);
         } else {
           r[0] = (T)acc[i][0]; r[1] = (T)acc[i][1];
@@ -114,10 +154,14 @@ __global__ __launch_bounds__(256) void dwconv_tiled_fwd_kernel(const T* __restri
         *reinterpret_cast<PT*>(y + o) = r;
       }
     }
+    if (MODE >= 2) {
+#pragma unroll
+      for (int i = 0; i < TXS; ++i) ax[i] = ax_next[i];
+    }
   }
 }
 
-template <typename T, int K> constexpr size_t fwd_lds() { return (size_t)(TY + K - 1) * (TXW + K - 1) * 128 * sizeof(T); }
+template <typename T, int K> constexpr size_t fwd_lds() { return (size_t)TileStage<T, K>::SLOTS * 16; }
 
 }  // namespace
 

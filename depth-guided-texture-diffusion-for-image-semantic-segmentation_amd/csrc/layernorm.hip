@@ -3,201 +3,225 @@
 //
 // HBM-bound: algorithmic bytes fwd = 2*e*rows*C, bwd = 3*e*rows*C (e = element size).
 // Mapping: a row is cut into 16-byte chunks; a power-of-two group of G lanes owns one row
-// (64/G rows per wave), every lane keeps its chunks in registers, moments are reduced with
-// wave shuffles inside the group.  No LDS in the forward.
+// (64/G rows per wave), every lane keeps its chunks in registers, moments are reduced inside
+// the group in registers (group_sum<G>, common.h).  No LDS in the forward.
+//
+// Most launches of the model are a single trip of a single wave of workgroups, so a launch lasts as long as the dependent chain
+// of one wave.  The kernels keep that chain short: every global load of a trip (gamma/beta, then the rows) is issued before the first
+// wait and none stands under a branch (idle lanes and the rows past the end load from a clamped address and select zero), the
+// reductions of all U rows and of both sums advance together, and the rows are stored after the last of them.
 #include "common.h"
 
 namespace {
 
 constexpr int LN_MAX_NPL = 4;      // chunks per lane: covers C <= 1024 (fp32) / 2048 (bf16)
 constexpr int LN_BWD_MAX_GRID = 1024;
+constexpr int ln_rows_in_flight(int npl) { return npl <= 2 ? 4 : 2; }   // U: rows per lane group and trip
 
-template <typename T>
-struct RowRegs {
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte load of a parameter vector that is only 4-byte aligned
+
+// which chunks of a row a lane owns: chunk gl + i*G for i < NPL; lanes past the row's end point at the last chunk and hold zeros
+template <typename T, int NPL, int G>
+struct LnLane {
   static constexpr int V = Vec16<T>::N;
-  float v[LN_MAX_NPL][V];
+  bool in[NPL];
+  int off[NPL];   // element offset of chunk i inside a row, clamped
+  __device__ __forceinline__ LnLane(int gl, int cpr) {
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { const int c = gl + i * G; in[i] = c < cpr; off[i] = (in[i] ? c : cpr - 1) * V; }
+  }
+  // the lane's columns of a per-column fp32 vector, zero in idle lanes
+  __device__ __forceinline__ void load_param(const float* __restrict__ p, float (&o)[NPL][V]) const {
+    f32x4 t[NPL][V / 4];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i)
+#pragma unroll
+      for (int k = 0; k < V / 4; ++k) t[i][k] = *reinterpret_cast<const f32x4_a4*>(p + off[i] + 4 * k);
+#pragma unroll
+    for (int i = 0; i < NPL; ++i)
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[i][j] = in[i] ? t[i][j / 4][j % 4] : 0.f;
+  }
 };
 
-template <typename T, int NPL>
-__device__ __forceinline__ void load_row(const T* __restrict__ p, int cpr, int gl, int G, float (&v)[NPL][Vec16<T>::N]) {
-  typedef typename Vec16<T>::type VT;
-  constexpr int V = Vec16<T>::N;
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    int c = gl + i * G;
-    if (c < cpr) {
-      VT t = *reinterpret_cast<const VT*>(p + (size_t)c * V);
-#pragma unroll
-      for (int j = 0; j < V; ++j) v[i][j] = (float)t[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j) v[i][j] = 0.f;
-    }
-  }
-}
-
-template <typename T, int NPL>
+template <typename T, int NPL, int G>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, T* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd,
-                                                     int64_t rows, int C, float eps, int G) {
+                                                     int64_t rows, int C, float eps) {
   typedef typename Vec16<T>::type VT;
-  constexpr int V = Vec16<T>::N;
-  const int cpr = C / V;
+  constexpr int V = Vec16<T>::N, U = ln_rows_in_flight(NPL), RPW = 64 / G, RPB = RPW * 4;   // rows per wave / per workgroup and u
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int gl = lane & (G - 1), gi = lane / G, rpw = 64 / G;
-  const int64_t rows_per_block = (int64_t)rpw * 4;
+  const int gl = lane & (G - 1), gi = lane / G;
   const float invC = 1.f / (float)C;
+  const LnLane<T, NPL, G> ll(gl, C / V);
   // per-lane gamma/beta (column mapping is row-independent)
   float gm[NPL][V], bt[NPL][V];
-#pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    int c = gl + i * G;
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      gm[i][j] = (c < cpr) ? gamma[c * V + j] : 0.f;
-      bt[i][j] = (c < cpr) ? beta[c * V + j] : 0.f;
-    }
-  }
-  constexpr int U = (NPL <= 2) ? 4 : 2;   // rows in flight per lane group: all row loads are issued before the first reduction
-  for (int64_t r0 = (int64_t)blockIdx.x * rows_per_block * U; r0 < rows; r0 += (int64_t)gridDim.x * rows_per_block * U) {
-    float v[U][NPL][V];
-    bool ok[U];
+  ll.load_param(gamma, gm);
+  ll.load_param(beta, bt);
+  for (int64_t r0 = (int64_t)blockIdx.x * RPB * U; r0 < rows; r0 += (int64_t)gridDim.x * RPB * U) {
+    VT t[U][NPL];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int64_t row = r0 + (int64_t)u * rows_per_block + wave * rpw + gi;
-      ok[u] = row < rows;
-      if (ok[u]) load_row<T, NPL>(x + row * C, cpr, gl, G, v[u]);
-      else {
+      const int64_t rr = r0 + u * RPB + wave * RPW + gi, row = rr < rows ? rr : rows - 1;
 #pragma unroll
-        for (int i = 0; i < NPL; ++i)
-#pragma unroll
-          for (int j = 0; j < V; ++j) v[u][i][j] = 0.f;
-      }
+      for (int i = 0; i < NPL; ++i) t[u][i] = *reinterpret_cast<const VT*>(x + row * C + ll.off[i]);
     }
+    float v[U][NPL][V], s[U], q[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int64_t row = r0 + (int64_t)u * rows_per_block + wave * rpw + gi;
-      float s = 0.f;
+      s[u] = 0.f;
 #pragma unroll
       for (int i = 0; i < NPL; ++i)
 #pragma unroll
-        for (int j = 0; j < V; ++j) s += v[u][i][j];
-      const float mu = group_sum(s, G) * invC;
-      float q = 0.f;
+        for (int j = 0; j < V; ++j) { v[u][i][j] = ll.in[i] ? (float)t[u][i][j] : 0.f; s[u] += v[u][i][j]; }
+    }
+    group_sum<G>(s);
 #pragma unroll
-      for (int i = 0; i < NPL; ++i) {
-        bool in = (gl + i * G) < cpr;
+    for (int u = 0; u < U; ++u) {
+      s[u] *= invC;   // mean
+      q[u] = 0.f;
 #pragma unroll
-        for (int j = 0; j < V; ++j) { float d = in ? v[u][i][j] - mu : 0.f; q += d * d; }
-      }
-      const float rs = rsqrtf(group_sum(q, G) * invC + eps);
-      if (ok[u]) {
+      for (int i = 0; i < NPL; ++i)
 #pragma unroll
-        for (int i = 0; i < NPL; ++i) {
-          int c = gl + i * G;
-          if (c < cpr) {
-            VT o;
+        for (int j = 0; j < V; ++j) { float d = ll.in[i] ? v[u][i][j] - s[u] : 0.f; q[u] = __builtin_fmaf(d, d, q[u]); }
+    }
+    group_sum<G>(q);
+    // every row's outputs come from the ONE copy of the arithmetic below (with its multiply-adds spelled out: which of them fuse is
+    // not left to the compiler, so a row's bits do not depend on its slot u); the workgroup-uniform branch after it only stores
+    VT o[U][NPL];
 #pragma unroll
-            for (int j = 0; j < V; ++j) o[j] = (T)((v[u][i][j] - mu) * rs * gm[i][j] + bt[i][j]);
-            *reinterpret_cast<VT*>(y + row * C + (size_t)c * V) = o;
-          }
-        }
-        if (gl == 0) { mean[row] = mu; rstd[row] = rs; }
-      }
+    for (int u = 0; u < U; ++u) {
+      q[u] = rsqrtf(__builtin_fmaf(q[u], invC, eps));
+#pragma unroll
+      for (int i = 0; i < NPL; ++i)
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[u][i][j] = (T)__builtin_fmaf((v[u][i][j] - s[u]) * q[u], gm[i][j], bt[i][j]);
+    }
+    auto store_row = [&](int u, int64_t row) {
+#pragma unroll
+      for (int i = 0; i < NPL; ++i)
+        if (ll.in[i]) *reinterpret_cast<VT*>(y + row * C + ll.off[i]) = o[u][i];
+      if (gl == 0) { mean[row] = s[u]; rstd[row] = q[u]; }
+    };
+    const int64_t first = r0 + wave * RPW + gi;
+    if (r0 + (int64_t)RPB * U <= rows) {       // workgroup-uniform: every row of the trip exists
+#pragma unroll
+      for (int u = 0; u < U; ++u) store_row(u, first + u * RPB);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (first + u * RPB < rows) store_row(u, first + u * RPB);
     }
   }
 }
 
 // Backward: dx per row; per-block partial dgamma/dbeta written to ws[block][2][C].
-template <typename T, int NPL>
+template <typename T, int NPL, int G>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const T* __restrict__ dres, T* __restrict__ dx,
-                                                     float* __restrict__ ws, int64_t rows, int C, int G) {
+                                                     float* __restrict__ ws, int64_t rows, int C) {
   typedef typename Vec16<T>::type VT;
-  constexpr int V = Vec16<T>::N;
+  constexpr int V = Vec16<T>::N, U = ln_rows_in_flight(NPL), RPW = 64 / G, RPB = RPW * 4;
   extern __shared__ float red[];  // [4 waves][2][C]
-  const int cpr = C / V;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int gl = lane & (G - 1), gi = lane / G, rpw = 64 / G;
-  const int64_t rows_per_block = (int64_t)rpw * 4;
+  const int gl = lane & (G - 1), gi = lane / G;
   const float invC = 1.f / (float)C;
+  const LnLane<T, NPL, G> ll(gl, C / V);
   float gm[NPL][V], dg[NPL][V], db[NPL][V];
 #pragma unroll
-  for (int i = 0; i < NPL; ++i) {
-    int c = gl + i * G;
+  for (int i = 0; i < NPL; ++i)
 #pragma unroll
-    for (int j = 0; j < V; ++j) { gm[i][j] = (c < cpr) ? gamma[c * V + j] : 0.f; dg[i][j] = 0.f; db[i][j] = 0.f; }
-  }
-  constexpr int U = (NPL <= 2) ? 4 : 2;   // rows in flight per lane group: U independent row loads are issued before any reduction
-  for (int64_t r0 = (int64_t)blockIdx.x * rows_per_block * U; r0 < rows; r0 += (int64_t)gridDim.x * rows_per_block * U) {
-    float xv[U][NPL][V], gv[U][NPL][V], mu[U], rs[U];
-    bool ok[U];
+    for (int j = 0; j < V; ++j) { dg[i][j] = 0.f; db[i][j] = 0.f; }
+  ll.load_param(gamma, gm);
+  for (int64_t r0 = (int64_t)blockIdx.x * RPB * U; r0 < rows; r0 += (int64_t)gridDim.x * RPB * U) {
+    VT tx[U][NPL], tg[U][NPL], tr[U][NPL];
+    float mu[U], rs[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int64_t row = r0 + (int64_t)u * rows_per_block + wave * rpw + gi;
-      ok[u] = row < rows;
-      if (ok[u]) {
-        load_row<T, NPL>(x + row * C, cpr, gl, G, xv[u]);
-        load_row<T, NPL>(dy + row * C, cpr, gl, G, gv[u]);
-        mu[u] = mean[row]; rs[u] = rstd[row];
-      } else {
-        mu[u] = 0.f; rs[u] = 0.f;
+      const int64_t rr = r0 + u * RPB + wave * RPW + gi, row = rr < rows ? rr : rows - 1;
 #pragma unroll
-        for (int i = 0; i < NPL; ++i)
+      for (int i = 0; i < NPL; ++i) {
+        tx[u][i] = *reinterpret_cast<const VT*>(x + row * C + ll.off[i]);
+        tg[u][i] = *reinterpret_cast<const VT*>(dy + row * C + ll.off[i]);
+      }
+      mu[u] = mean[row]; rs[u] = rstd[row];
+    }
+    if (dres) {      // gradient of the residual branch that forks off x (kernel-uniform)
 #pragma unroll
-          for (int j = 0; j < V; ++j) { xv[u][i][j] = 0.f; gv[u][i][j] = 0.f; }
+      for (int u = 0; u < U; ++u) {
+        const int64_t rr = r0 + u * RPB + wave * RPW + gi, row = rr < rows ? rr : rows - 1;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) tr[u][i] = *reinterpret_cast<const VT*>(dres + row * C + ll.off[i]);
       }
     }
+    const int64_t first = r0 + wave * RPW + gi;
+    const bool full = r0 + (int64_t)RPB * U <= rows;     // workgroup-uniform: every row of the trip exists
+    float xv[U][NPL][V], gv[U][NPL][V], ab[2 * U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      const bool ok = full || first + u * RPB < rows;    // a row past the end adds zeros to dgamma/dbeta
       float a = 0.f, b = 0.f;
 #pragma unroll
       for (int i = 0; i < NPL; ++i) {
-        bool in = (gl + i * G) < cpr;
+        const bool in = ll.in[i] && ok;
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-          float xh = in ? (xv[u][i][j] - mu[u]) * rs[u] : 0.f;
-          float g = gv[u][i][j];
-          dg[i][j] += g * xh;
+          float xh = in ? ((float)tx[u][i][j] - mu[u]) * rs[u] : 0.f;
+          float g = in ? (float)tg[u][i][j] : 0.f;
+          dg[i][j] = __builtin_fmaf(g, xh, dg[i][j]);
           db[i][j] += g;
           g *= gm[i][j];
-          a += g; b += g * xh;
+          a += g; b = __builtin_fmaf(g, xh, b);
           xv[u][i][j] = xh; gv[u][i][j] = g;
         }
       }
-      a = group_sum(a, G) * invC;
-      b = group_sum(b, G) * invC;
-      if (ok[u]) {
-        const int64_t row = r0 + (int64_t)u * rows_per_block + wave * rpw + gi;
+      ab[2 * u] = a; ab[2 * u + 1] = b;
+    }
+    group_sum<G>(ab);
+    // every row's dx comes from the ONE copy of the arithmetic below, multiply-adds spelled out (see the forward); the
+    // workgroup-uniform branch after it only stores
+    VT o[U][NPL];
 #pragma unroll
-        for (int i = 0; i < NPL; ++i) {
-          int c = gl + i * G;
-          if (c < cpr) {
-            VT o, r;
-            if (dres) r = *reinterpret_cast<const VT*>(dres + row * C + (size_t)c * V);   // gradient of the residual branch that forks off x
+    for (int u = 0; u < U; ++u) {
+      const float a = ab[2 * u] * invC, b = ab[2 * u + 1] * invC;
 #pragma unroll
-            for (int j = 0; j < V; ++j) o[j] = (T)(rs[u] * (gv[u][i][j] - a - xv[u][i][j] * b) + (dres ? (float)r[j] : 0.f));
-            *reinterpret_cast<VT*>(dx + row * C + (size_t)c * V) = o;
-          }
-        }
-      }
+      for (int i = 0; i < NPL; ++i)
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+          o[u][i][j] = (T)__builtin_fmaf(rs[u], __builtin_fmaf(-xv[u][i][j], b, gv[u][i][j] - a), dres ? (float)tr[u][i][j] : 0.f);
+    }
+    auto store_row = [&](int u, int64_t row) {
+#pragma unroll
+      for (int i = 0; i < NPL; ++i)
+        if (ll.in[i]) *reinterpret_cast<VT*>(dx + row * C + ll.off[i]) = o[u][i];
+    };
+    if (full) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) store_row(u, first + u * RPB);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (first + u * RPB < rows) store_row(u, first + u * RPB);
     }
   }
   // combine the 64/G row-groups of the wave (same column set), then the 4 waves through LDS
 #pragma unroll
-  for (int i = 0; i < NPL; ++i)
-#pragma unroll
-    for (int j = 0; j < V; ++j)
-      for (int o = G; o < 64; o <<= 1) { dg[i][j] += __shfl_xor(dg[i][j], o, 64); db[i][j] += __shfl_xor(db[i][j], o, 64); }
+  for (int i = 0; i < NPL; ++i) {
+    if constexpr (G <= 1)  { lane_xor_add<1>(dg[i]);  lane_xor_add<1>(db[i]); }
+    if constexpr (G <= 2)  { lane_xor_add<2>(dg[i]);  lane_xor_add<2>(db[i]); }
+    if constexpr (G <= 4)  { lane_xor_add<4>(dg[i]);  lane_xor_add<4>(db[i]); }
+    if constexpr (G <= 8)  { lane_xor_add<8>(dg[i]);  lane_xor_add<8>(db[i]); }
+    if constexpr (G <= 16) { lane_xor_add<16>(dg[i]); lane_xor_add<16>(db[i]); }
+    if constexpr (G <= 32) { lane_xor_add<32>(dg[i]); lane_xor_add<32>(db[i]); }
+  }
   if (gi == 0) {
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
-      int c = gl + i * G;
-      if (c < cpr)
+      if (ll.in[i])
 #pragma unroll
-        for (int j = 0; j < V; ++j) { red[(wave * 2 + 0) * C + c * V + j] = dg[i][j]; red[(wave * 2 + 1) * C + c * V + j] = db[i][j]; }
+        for (int j = 0; j < V; ++j) { red[(wave * 2 + 0) * C + ll.off[i] + j] = dg[i][j]; red[(wave * 2 + 1) * C + ll.off[i] + j] = db[i][j]; }
     }
   }
   __syncthreads();
@@ -219,6 +243,16 @@ template <typename T> LnGeom ln_geom(int C) {
   return g;
 }
 
+// run STMT with NPL_ / G_ bound to the geometry: more than one chunk per lane occurs only with full-wave groups
+#define LN_DISPATCH(g, STMT) do { \
+    if ((g).G == 64) { constexpr int G_ = 64; \
+      if ((g).npl == 1) { constexpr int NPL_ = 1; STMT; } else if ((g).npl == 2) { constexpr int NPL_ = 2; STMT; } \
+      else if ((g).npl == 3) { constexpr int NPL_ = 3; STMT; } else { constexpr int NPL_ = 4; STMT; } } \
+    else { constexpr int NPL_ = 1; \
+      if ((g).G == 32) { constexpr int G_ = 32; STMT; } else if ((g).G == 16) { constexpr int G_ = 16; STMT; } \
+      else if ((g).G == 8) { constexpr int G_ = 8; STMT; } else if ((g).G == 4) { constexpr int G_ = 4; STMT; } \
+      else if ((g).G == 2) { constexpr int G_ = 2; STMT; } else { constexpr int G_ = 1; STMT; } } } while (0)
+
 template <typename T>
 int ln_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                   int64_t rows, int C, float eps, hipStream_t s) {
@@ -226,11 +260,8 @@ int ln_fwd_launch(const void* x, const float* gamma, const float* beta, void* y,
   LnGeom g = ln_geom<T>(C);
   DGTD_REQUIRE(g.npl <= LN_MAX_NPL, "layernorm: C=%d too large", C);
   if (rows == 0) return 0;
-  const int U = g.npl <= 2 ? 4 : 2;     // must match ln_fwd_kernel
-  int grid = (int)std::min<int64_t>(cdiv(rows, g.rows_per_block * U), 256 * 8);
-#define LN_FWD(NPL) hipLaunchKernelGGL((ln_fwd_kernel<T, NPL>), dim3(grid), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, mean, rstd, rows, C, eps, g.G)
-  switch (g.npl) { case 1: LN_FWD(1); break; case 2: LN_FWD(2); break; case 3: LN_FWD(3); break; default: LN_FWD(4); }
-#undef LN_FWD
+  int grid = (int)std::min<int64_t>(cdiv(rows, g.rows_per_block * ln_rows_in_flight(g.npl)), 256 * 8);
+  LN_DISPATCH(g, hipLaunchKernelGGL((ln_fwd_kernel<T, NPL_, G_>), dim3(grid), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, mean, rstd, rows, C, eps));
   DGTD_CHECK_LAUNCH("layernorm_fwd");
   return 0;
 }
@@ -244,9 +275,7 @@ int ln_bwd_launch(const void* dy, const void* x, const float* gamma, const float
   DGTD_REQUIRE(rows > 0, "layernorm_bwd: rows must be > 0");
   int grid = (int)std::min<int64_t>(cdiv(rows, g.rows_per_block * 4), LN_BWD_MAX_GRID);
   size_t lds = (size_t)4 * 2 * C * sizeof(float);
-#define LN_BWD(NPL) hipLaunchKernelGGL((ln_bwd_kernel<T, NPL>), dim3(grid), dim3(256), lds, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)dres, (T*)dx, (float*)ws, rows, C, g.G)
-  switch (g.npl) { case 1: LN_BWD(1); break; case 2: LN_BWD(2); break; case 3: LN_BWD(3); break; default: LN_BWD(4); }
-#undef LN_BWD
+  LN_DISPATCH(g, hipLaunchKernelGGL((ln_bwd_kernel<T, NPL_, G_>), dim3(grid), dim3(256), lds, s, (const T*)dy, (const T*)x, gamma, mean, rstd, (const T*)dres, (T*)dx, (float*)ws, rows, C));
   DGTD_CHECK_LAUNCH("layernorm_bwd");
   if (nblocks) { *nblocks = grid; return 0; }
   const dgtd_reduce_entry e{(const float*)ws, grid, 2 * C, dgamma, C, dbeta, DGTD_F32, 0, 0, nullptr};     // ws [grid][2C] = { dgamma | dbeta } partial rows
